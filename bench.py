@@ -21,6 +21,18 @@ Workloads
   c5            one multi-frame window of --window frames (default 1024) sharded over the GPUs, shared
                 beta, L2 pose prior + temporal links, one all-reduce of [cost, g_beta, H_bb] per step
                 ("scaling": "strong").  BASELINE.json configs[4].
+
+Plain run and --full
+  A plain run does what the headline needs and nothing else: set-up, --prewarm untimed sweeps, --warmup steps, ONE bracket of
+  exactly --steps timed steps (ms_per_step = that bracket / --steps), the check that every timed sweep completed, the outputs
+  (--dump-outputs) and the line.  --full adds everything else this bench measures, as before: the cold-start bracket, the
+  median of --repeats (default 9) brackets, per-kernel durations, the launch period and the roofline, c5_strong, the PCIe and
+  Ceres-path rates, the CPU baseline and the fits.
+--dump-outputs DIR
+  after the timed steps, rank 0 writes what the last timed step computed (residuals, Jacobian, mixture components, posed joints,
+  cloud; the shared reduction for c5; the fitted parameters for --fit) as DIR/<name>.npy in float32 / float64, at most
+  DUMP_BUDGET bytes in all (above that, a fixed seeded sample of rows, named in DIR/<name>_rows.npy).  The inputs are seeded:
+  the same arguments give the same inputs in every run.
 """
 import argparse
 import importlib
@@ -42,6 +54,54 @@ B_MODEL_MESH = 82_680 + 826_800 + 17_114_760 + 661_440      # v_template + shape
 B_MODEL_ALL = B_MODEL_MESH + 661_440                         # + dense J_regressor (whole pipeline figure)
 B_FRAME_MESH = 82_680 + 24 * 12 * 4 + 217 * 4                # cloud out + skin transforms + blend coefficients
 B_FRAME_ALL = 118_588                                        # params 608 + kps 500 + r 400 + J 34,400 + cloud 82,680
+DUMP_BUDGET = 60_000_000   # --dump-outputs: bytes of array data in all (under 64 MB with the .npy headers and row indices)
+
+
+def _d2h(ptr, shape, dtype):
+    """A device buffer of the library copied into a new host array; the caller has waited for the stream that wrote it.
+    hipMemcpy is looked up through libbodyfit.so's handle, i.e. in the HIP runtime the library itself runs on."""
+    import ctypes
+    api = importlib.import_module("3dbodyanimation_amd.api")
+    a = np.empty(shape, dtype)
+    if a.nbytes:
+        fn = api.load_library().hipMemcpy
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        fn.restype = ctypes.c_int
+        rc = fn(a.ctypes.data, ptr, a.nbytes, 2)   # 2: hipMemcpyDeviceToHost
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy of a {a.nbytes}-byte output failed: error {rc}")
+    return a
+
+
+def sweep_outputs(prob, gm, d_red=None):
+    """What the last sweep of `prob` left in its device buffers (bodyfit_problem_views): what a caller of the sweep receives."""
+    v, L, F = prob.views(), prob.layout, prob.n_frames
+    out = {"residuals": _d2h(v.residuals, (L.total_rows,), np.float64),
+           "jacobian": _d2h(v.jacobian, (L.reproj_rows, L.n_cols), np.float64),
+           "gmm_comp": _d2h(v.gmm_comp, (F,), np.int32).astype(np.float64),
+           "joints": _d2h(v.joints, (F, gm.n_joints, 3), np.float64)}
+    if prob.want_mesh:
+        out["cloud"] = _d2h(v.cloud, (F, v.cloud_frame_stride), np.float32)[:, :3 * gm.n_verts].reshape(F, gm.n_verts, 3)
+    if d_red is not None:
+        out["shared_reduction"] = d_red.cpu().numpy().astype(np.float64)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy.  When they hold more than DUMP_BUDGET bytes in all, each array of 1 MB
+    or more keeps the same fraction of its rows (axis 0), drawn by a fixed seed and kept in order; out_dir/<name>_rows.npy
+    lists them."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes < 2**20)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if total > DUMP_BUDGET and a.nbytes >= 2**20:
+            keep = max(1, int(a.shape[0] * 0.95 * (DUMP_BUDGET - small) / (total - small)))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(synth, model, seq, F_sample, gmm_np, beta_pose=20.0, beta_shape=30.0):
@@ -196,20 +256,23 @@ def c5_fit(args, api, synth, model, gm, dist, rank, world, local_rank):
         t = torch.tensor([dt], dtype=torch.float64, device=torch.device("cuda", local_rank) if backend == "nccl" else None)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the Jacobian sweep of the shard (the evaluator inside the fit), timed with HIP events for the roofline object
-    dev = torch.device("cuda", local_rank)
-    d_params = torch.from_numpy(np.ascontiguousarray(x0)).to(dev)
-    d_beta = torch.zeros(10, dtype=torch.float64, device=dev)
-    prof = prob.profile_sweep(d_params.data_ptr(), d_beta.data_ptr(), True, False, 50, torch.cuda.current_stream().cuda_stream)
+    if args.dump_outputs and rank == 0:   # the last timed fit's result: this rank's frames and the shared beta
+        dump_outputs(args.dump_outputs, {"params": np.asarray(x, np.float64), "beta": np.asarray(b, np.float64),
+                                         "cost": np.array([summ.initial_cost, summ.final_cost], np.float64)})
+    prof = None
+    if args.full:
+        # the Jacobian sweep of the shard (the evaluator inside the fit), timed with HIP events for the roofline object
+        dev = torch.device("cuda", local_rank)
+        d_params = torch.from_numpy(np.ascontiguousarray(x0)).to(dev)
+        d_beta = torch.zeros(10, dtype=torch.float64, device=dev)
+        prof = prob.profile_sweep(d_params.data_ptr(), d_beta.data_ptr(), True, False, 50, torch.cuda.current_stream().cuda_stream)
     if rank == 0:
         F = shard.n_local
-        alg = F * (608 + 80 + 500 + 400 + 34_400)
-        a = alg / (prof["frame_resjac"] * 1e-3) / 1e9
         ms_fit = dt / args.steps * 1e3
         out = {
             "metric": "frames/sec to convergence (multi-frame window, shared beta)", "value": Fw * args.steps / dt, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_fit, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"C5 fit: one {Fw}-frame multi-frame window (3dba_multi residual blocks: 25 keypoints per frame, "
                                    f"shared beta, L2 pose prior 5, shape prior 25, temporal 3) fitted to convergence, frames sharded "
                                    f"over {world} GPU(s)", "window": Fw, "frames_per_gpu": F, "keypoints_per_frame": 25, "n_cols": 86},
@@ -219,12 +282,15 @@ def c5_fit(args, api, synth, model, gm, dist, rank, world, local_rank):
                     "exchanges_per_iteration": 0 if world == 1 else "3 all-gathers on device buffers: interface blocks + beta terms (225 KB per rank), beta Schur partials (110 doubles), scalars (8 doubles)",
                     "exchanges_total": 0 if world == 1 else prob.last_exchange_count(),
                     "transport": None if world == 1 else ("RCCL ncclAllGather on the solve's stream" if rccl is not None else "host callbacks over gloo (rehearsal)")},
-            "roofline": {"bound": "hbm", "kernel": "frame_resjac", "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": a / HBM_PEAK_GBS, "traffic": None, "traffic_source": None,
-                         "algorithmic_bytes_per_launch": alg, "avg_launch_ms": prof["frame_resjac"],
-                         "note": "the Jacobian sweep of one shard inside the fit (no mesh); a fit iteration is latency-bound: "
-                                 "cyclic-reduction levels of 76 x 76 f64 block factorisations"},
         }
+        if prof is not None:
+            alg = F * (608 + 80 + 500 + 400 + 34_400)
+            a = alg / (prof["frame_resjac"] * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": "frame_resjac", "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": a / HBM_PEAK_GBS, "traffic": None, "traffic_source": None,
+                               "algorithmic_bytes_per_launch": alg, "avg_launch_ms": prof["frame_resjac"],
+                               "note": "the Jacobian sweep of one shard inside the fit (no mesh); a fit iteration is latency-bound: "
+                                       "cyclic-reduction levels of 76 x 76 f64 block factorisations"}
         print(json.dumps(out), file=RECORD_OUT, flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -444,9 +510,14 @@ def main():
     ap.add_argument("--prewarm-rest-ms", type=float, default=0.0,
                     help="idle time in front of each timed bracket's warm-up steps (round 4 tuned 2 ms against the clock governor; "
                          "the median over --repeats brackets makes it unnecessary: default 0)")
-    ap.add_argument("--repeats", type=int, default=9,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="how many times the contract's bracket (barrier + synchronize, K steps, synchronize + barrier) is timed; "
-                         "ms_per_step = the median bracket, min / max are reported beside it")
+                         "ms_per_step = the median bracket, min / max are reported beside it (default 1; 9 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: cold-start bracket, repeated brackets, per-kernel durations and roofline, "
+                         "c5_strong, PCIe and Ceres-path rates, CPU baseline, fits (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pcie", action="store_true", help="(kept for old command lines: the host-pointer rate is always reported)")
     ap.add_argument("--no-ceres-path", action="store_true", help="skip the Ceres-kept-path record (needs g++ on the box)")
@@ -458,6 +529,8 @@ def main():
                     help="with --workload c5: a step is one complete LM fit of the window (frames/sec to convergence), sharded "
                          "over the GPUs by bodyfit_solve_sharded; defaults then to --steps 5 --warmup 1")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
     if args.fit and args.workload == "c5":
         if "--steps" not in sys.argv:
             args.steps = 5
@@ -582,11 +655,13 @@ def main():
             dt = float(t.item())
         return dt
 
-    # (1) the contract read literally, on a process that has done nothing yet: W warm-up steps, K timed steps.  Reported as
-    # `cold_start` beside the headline (a fresh process's first ~500 launches run on the clock ramp: 23-25 us per step)
-    for _ in range(args.warmup):
-        step()
-    dt_cold = bracket(args.steps)
+    # (1) --full: the contract read literally, on a process that has done nothing yet: W warm-up steps, K timed steps.  Reported
+    # as `cold_start` beside the headline (a fresh process's first ~500 launches run on the clock ramp: 23-25 us per step)
+    dt_cold = None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        dt_cold = bracket(args.steps)
     # (2) untimed sweeps until the clock (and the caches' view of the model) have settled ...
     for i in range(args.prewarm):
         prob.evaluate_device(d_params.data_ptr(), d_beta.data_ptr(), True, stream)
@@ -595,7 +670,8 @@ def main():
     torch.cuda.synchronize()
     # (3) ... then the contract's bracket `--repeats` times (W warm-up steps in front of each); `ms_per_step` is the MEDIAN bracket,
     # the spread goes into the line.  No governor-tuned rest any more: a 0.4 ms timed region read once depends on where the
-    # clock governor happens to be (one run in four read 23 us in round 4), the median of seven does not
+    # clock governor happens to be (one run in four read 23 us in round 4), the median of seven does not.  A plain run times
+    # one bracket: exactly --steps timed steps
     dts = []
     for _ in range(max(1, args.repeats)):
         if args.prewarm_rest_ms > 0:
@@ -609,86 +685,41 @@ def main():
     # leaves tiles of the cloud unwritten in a FASTER step.)  The run fails when one did not; the count goes into the line.
     prob.sweep_status(stream)
     sweep_timeouts = prob.sweep_timeouts()
+    if args.dump_outputs and rank == 0:   # the buffers still hold the last timed step's results (every step computes the same)
+        dump_outputs(args.dump_outputs, sweep_outputs(prob, gm, d_red if with_reduce else None))
 
-    # per-kernel durations with HIP events on the launch stream (same inputs, same stream), right behind the timed steps — the
-    # same warm device — and over at least 100 launches
-    prof = prob.profile_sweep(d_params.data_ptr(), d_beta.data_ptr(), True, with_reduce, max(100, min(400, args.steps)), stream)
-    # ... and the kernel's launch PERIOD, by two HIP events on the same stream around a run of back-to-back sweeps: what a launch
-    # costs in steady state (the dispatch's own begin -> end, which profile_sweep reads, plus the dependent-launch boundary of
-    # ~1.2 us).  This is the figure all three clocks reproduce — the K-step timing above, these events, and rocprofv3's kernel
-    # trace of the same command (profiles/<tag>_kernel_stats_post_prewarm.json), whose per-dispatch durations under the tracer
-    # read as the period, not as the bare begin -> end (r5_00: 20.23 us traced against 18.86 us begin -> end and a 20.03 us
-    # period untraced) — so `roofline` is computed from it; the bare figure stays beside it as `kernel_only`.
-    n_ev = max(100, min(400, args.steps))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(10):
-        step()
-    ev0.record(work_stream)
-    for _ in range(n_ev):
-        step()
-    ev1.record(work_stream)
-    torch.cuda.synchronize()
-    period_ms = ev0.elapsed_time(ev1) / n_ev
-    prob.sweep_status(stream)
-    sweep_timeouts = prob.sweep_timeouts()
+    prof = period_ms = n_ev = strong = None
+    if args.full:
+        # per-kernel durations with HIP events on the launch stream (same inputs, same stream), right behind the timed steps —
+        # the same warm device — and over at least 100 launches
+        prof = prob.profile_sweep(d_params.data_ptr(), d_beta.data_ptr(), True, with_reduce, max(100, min(400, args.steps)), stream)
+        # ... and the kernel's launch PERIOD, by two HIP events on the same stream around a run of back-to-back sweeps: what a
+        # launch costs in steady state (the dispatch's own begin -> end, which profile_sweep reads, plus the dependent-launch
+        # boundary of ~1.2 us).  This is the figure all three clocks reproduce — the K-step timing above, these events, and
+        # rocprofv3's kernel trace of the same command (profiles/<tag>_kernel_stats_post_prewarm.json), whose per-dispatch
+        # durations under the tracer read as the period, not as the bare begin -> end (r5_00: 20.23 us traced against 18.86 us
+        # begin -> end and a 20.03 us period untraced) — so `roofline` is computed from it; the bare figure stays beside it as
+        # `kernel_only`.
+        n_ev = max(100, min(400, args.steps))
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(10):
+            step()
+        ev0.record(work_stream)
+        for _ in range(n_ev):
+            step()
+        ev1.record(work_stream)
+        torch.cuda.synchronize()
+        period_ms = ev0.elapsed_time(ev1) / n_ev
+        prob.sweep_status(stream)
+        sweep_timeouts = prob.sweep_timeouts()
 
-    # configs[4] on the same ranks, in the same line (default workload only: `value` stays the C3 figure at every N)
-    strong = None
-    if args.workload == "c3" and not args.no_c5_strong:
-        strong = c5_strong(args, api, synth, model, gm, dist, rank, world, local_rank)
+        # configs[4] on the same ranks, in the same line (default workload only: `value` stays the C3 figure at every N)
+        if args.workload == "c3" and not args.no_c5_strong:
+            strong = c5_strong(args, api, synth, model, gm, dist, rank, world, local_rank)
 
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         evals_s = total_frames * args.steps / dt
-        # algorithmic bytes per launch: what each kernel must read and write once
-        alg = {"mesh_blend_lbs": B_MODEL_MESH + F * B_FRAME_MESH,
-               "frame_resjac": F * (608 + 80 + 500 + 400 + 34_400 + 24 * 12 * 4 + 217 * 4)}
-        pmc_name = {"mesh_blend_lbs": "k_mesh_blend_lbs", "frame_resjac": "k_frame_resjac", "sweep_roles": "k_sweep_roles"}
-        fused = prof.get("sweep_roles", 0.0) > 0.0
-        if fused:
-            # the sweep was ONE launch (frame, mesh and prior roles side by side): the kernel IS the pipeline, so its algorithmic
-            # bytes are SURVEY.md 8d's B(F) = B_model + F B_frame exactly (49,705,648 B at 256 frames) — the same figure
-            # `pipeline` divides by the step time.  (Rounds 2-3 summed the two launches' own figures here, which count the
-            # in-launch hand-off — transforms + coefficients, 2,020 B per frame — on both sides and leave the dense J_regressor out:
-            # +0.8 %.)
-            alg = {"sweep_roles": B_MODEL_ALL + F * B_FRAME_ALL}
-        # HBM bytes per launch: rocprofv3 cannot run inside this process, so `traffic` is what the committed --pmc passes
-        # of THIS command measured (tools/profile_round.sh writes profiles/rN_xx_pmc_traffic.json: FETCH_SIZE doubled per the
-        # gfx950 note + WRITE_SIZE); `traffic_source` names that file.  Null when no committed pass matches the workload
-        # and size, or its kernel names are not the ones this build launches.
-        pm = pm_src = None
-        try:
-            import glob
-            pm_src = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")))[-1]
-            pm = json.load(open(pm_src))
-            if not (args.workload == pm["workload"] and F == pm["frames_per_gpu"]):
-                pm = None
-        except Exception:
-            pm = None
-        kernels = {}
-        for k in alg:
-            # one launch per step (and no reduce launch): the launch period of the step's events IS this kernel's
-            dur = period_ms if (fused and not with_reduce) else prof[k]
-            a = alg[k] / (dur * 1e-3) / 1e9
-            ko = alg[k] / (prof[k] * 1e-3) / 1e9
-            kernels[k] = {"achieved": a, "frac": a / HBM_PEAK_GBS, "frac_of_measured_copy_rate": a / HBM_COPY_GBS,
-                          "algorithmic_bytes_per_launch": alg[k], "avg_launch_ms": dur,
-                          "avg_launch_ms_definition": ("launch period: two HIP events around %d back-to-back launches on the launch "
-                                                       "stream" % n_ev) if dur is period_ms else "dispatch begin -> end (HIP events)",
-                          "kernel_only": {"avg_launch_ms": prof[k], "achieved": ko, "frac": ko / HBM_PEAK_GBS,
-                                          "definition": "the dispatch's own begin -> end timestamps (hipExtLaunchKernelGGL events), "
-                                                        "without the dependent-launch boundary"},
-                          "traffic": pm["kernels"].get(pmc_name[k], {}).get("hbm_bytes") if pm else None}
-        # matrix-pipe view of the mesh kernel: the blend contraction is 2 x 20670 x 217 flop per frame; it is
-        # executed as three bf16 products per k-step on v_mfma_f32_32x32x16_bf16 (216 tiles x 14 k-steps x 9 MFMAs per 32 frames)
-        alg_flop = 2.0 * 20670 * 217 * F
-        exe_flop = 216 * ((F + 31) // 32) * 14 * 9 * 2.0 * 32 * 32 * 16
-        mk = "sweep_roles" if fused else "mesh_blend_lbs"
-        kernels[mk]["mfma"] = {
-            "algorithmic_TFLOPs": alg_flop / (prof[mk] * 1e-3) / 1e12, "f32_mfma_peak_TFLOPs": 157.3,
-            "executed_bf16_TFLOPs": exe_flop / (prof[mk] * 1e-3) / 1e12, "bf16_dense_peak_TFLOPs": 2500.0}
-        dom = max(alg, key=lambda k: prof[k])
-        bytes_launch, ach, traffic = alg[dom], kernels[dom]["achieved"], kernels[dom]["traffic"]
         whole = (B_MODEL_ALL + F * B_FRAME_ALL) / (ms_step * 1e-3) / 1e9
         out = {
             "metric": "SMPL residual+Jacobian evals/sec (6890v, 10 beta, 24 joints)",
@@ -696,78 +727,132 @@ def main():
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             # how ms_per_step was taken: the contract's bracket (barrier + synchronize, K steps, synchronize + barrier; MAX over
             # ranks) `repeats` times behind `prewarm_steps` untimed sweeps, each with its W warm-up steps in front; ms_per_step and
-            # value are the MEDIAN bracket.  cold_start: the same bracket as the process's very first work (W warm-up steps only)
+            # value are the MEDIAN bracket (a plain run: the one bracket).  --full adds cold_start: the same bracket as the
+            # process's very first work (W warm-up steps only)
             "timing": {"repeats": len(dts), "prewarm_steps": args.prewarm, "rest_ms_before_each_bracket": args.prewarm_rest_ms,
                        "ms_per_step_min": dts_sorted[0] / args.steps * 1e3, "ms_per_step_median": ms_step,
                        "ms_per_step_max": dts_sorted[-1] / args.steps * 1e3,
-                       "ms_per_step_all": [d / args.steps * 1e3 for d in dts],
-                       "cold_start": {"ms_per_step": dt_cold / args.steps * 1e3, "value": total_frames * args.steps / dt_cold,
-                                      "note": "W warm-up + K timed steps as the first GPU work of the process (clock ramp, cold caches)"}},
+                       "ms_per_step_all": [d / args.steps * 1e3 for d in dts]},
             "sweep_timeouts": sweep_timeouts,
             "dtype": "f64 residual/Jacobian; f32 mesh (f32 + split-bf16 MFMA blend)", "data": "synthetic",
             "config": {"workload": wl_name, "frames_per_gpu": F, "keypoints_per_frame": 25, "n_cols": 86},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach / HBM_PEAK_GBS, "frac_of_measured_copy_rate": ach / HBM_COPY_GBS, "traffic": traffic,
-                         "traffic_source": (os.path.relpath(pm_src, ROOT) + " (rocprofv3 --pmc passes of this command, "
-                                            "committed; not measured in this run)") if pm else None,
-                         "algorithmic_bytes_per_launch": bytes_launch, "avg_launch_ms": kernels[dom]["avg_launch_ms"],
-                         "avg_launch_ms_definition": kernels[dom]["avg_launch_ms_definition"],
-                         "kernel_only": kernels[dom]["kernel_only"],
-                         "algorithmic_bytes_definition": ("SURVEY.md 8d: B(F) = 19,347,120 (f32 model tensors, read once per launch) + "
-                                                         "F x 118,588 (params, keypoints, r, J, posed vertices)") if fused else
-                                                        "per kernel: the model tensors it reads + its per-frame inputs and outputs",
-                         "kernels": kernels},
-            "kernel_ms": prof,
             "pipeline": {"algorithmic_bytes_per_step": B_MODEL_ALL + F * B_FRAME_ALL, "achieved_GBps": whole,
                          "frac_of_hbm_peak": whole / HBM_PEAK_GBS, "frac_of_measured_copy_rate": whole / HBM_COPY_GBS},
+            "full": args.full,
         }
-        if strong is not None:
-            out["c5_strong"] = strong
-        if world == 1:
-            # the rate a kept ceres::Solve would see: host parameters up, one sweep, residuals + Jacobian down (page-locked
-            # mirrors, the problem's own stream); never `value`
-            # (cache_sweep: what bodyfit_ceres::SweepCallback::PrepareForEvaluation does — the sweep stays in the problem's
-            #  page-locked cache for the blocks' Evaluate calls, the Jacobian goes down as its non-zero column blocks;
-            #  ..._dense: the same with the dense [2K][86] panel copied out into the caller's numpy arrays)
-            for _ in range(3):
-                prob.cache_sweep(params_h, beta_h)
-            t1 = time.perf_counter()
-            for _ in range(50):
-                prob.cache_sweep(params_h, beta_h)
-            out["pcie_inclusive_evals_per_s"] = F * 50 / (time.perf_counter() - t1)
-            for _ in range(3):
-                prob.evaluate(params_h, beta_h, True)
-            t1 = time.perf_counter()
-            for _ in range(20):
-                prob.evaluate(params_h, beta_h, True)
-            out["pcie_inclusive_dense_evals_per_s"] = F * 20 / (time.perf_counter() - t1)
-            if args.workload == "c3" and not args.no_ceres_path:
-                out["ceres_path"] = ceres_path(synth, model, seq, F, evals_s)
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
-            n_cpu = args.cpu_sample_frames or min(F, 256)
-            cseq = seq if args.workload == "c3" else synth.make_sequence(model, n_cpu, seed=0)
-            out["cpu_baseline"] = cpu_baseline(synth, model, cseq, n_cpu, (w, mu, cov) if args.workload == "c3" else None,
-                                               beta_pose=20.0 if args.workload == "c3" else 5.0,
-                                               beta_shape=30.0 if args.workload == "c3" else 0.0)
-        if not args.no_fit and world == 1 and args.workload == "c3":
-            # the second half of BASELINE.json's metric: frames/sec to convergence of the product's LM on c2 / c3 / c4
-            # (tools/fit_bench.py; reference hooks src/main_single_frame.cpp:234-249,265-269), and the checker's own fits
-            # (oracle evaluator under the dense numpy LM) on a bounded sample beside them
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import fit_bench
-            # every record: median of its repeats, final robustified cost per stage, launches and microseconds per LM iteration;
-            # c4 and c5_staged both go through drivers.run_multi (the reference's staging incl. the write-back after every
-            # solve); c5_window is configs[4] as ONE 1024-frame window (what --workload c5 --fit shards over the ranks)
-            fit = {"unit": "frames/s", "c2": fit_bench.fit_c2(api, synth, model, gm),
-                   "c3": fit_bench.fit_c3(api, synth, model, gm), "c4": fit_bench.fit_c4(api, synth, model, gm),
-                   "window_20": fit_bench.fit_window(api, synth, model, gm, 20, 60),
-                   "c5_staged": fit_bench.fit_c5(api, synth, model, gm), "c5_window": fit_bench.fit_c5_window(api, synth, model, gm)}
-            if not args.no_cpu_baseline:
-                # eight threads: what the reference itself configures (options.num_threads = 8, include/MultiFrameBA.h:148;
-                # 4 in include/Sim3BA.h:476) — and what these small problems can use: 25 to 500 residual blocks per evaluation
-                # on all 256 hardware threads of the box is ten times SLOWER (fork/join of the OpenMP pool per evaluation)
-                fit["cpu_baseline"] = fit_bench.cpu_fit_baseline(synth, model, threads=min(8, os.cpu_count() or 8))
-            out["fit"] = fit
+        if args.full:
+            out["timing"]["cold_start"] = {"ms_per_step": dt_cold / args.steps * 1e3, "value": total_frames * args.steps / dt_cold,
+                                           "note": "W warm-up + K timed steps as the first GPU work of the process (clock ramp, "
+                                                   "cold caches)"}
+            # algorithmic bytes per launch: what each kernel must read and write once
+            alg = {"mesh_blend_lbs": B_MODEL_MESH + F * B_FRAME_MESH,
+                   "frame_resjac": F * (608 + 80 + 500 + 400 + 34_400 + 24 * 12 * 4 + 217 * 4)}
+            pmc_name = {"mesh_blend_lbs": "k_mesh_blend_lbs", "frame_resjac": "k_frame_resjac", "sweep_roles": "k_sweep_roles"}
+            fused = prof.get("sweep_roles", 0.0) > 0.0
+            if fused:
+                # the sweep was ONE launch (frame, mesh and prior roles side by side): the kernel IS the pipeline, so its algorithmic
+                # bytes are SURVEY.md 8d's B(F) = B_model + F B_frame exactly (49,705,648 B at 256 frames) — the same figure
+                # `pipeline` divides by the step time.  (Rounds 2-3 summed the two launches' own figures here, which count the
+                # in-launch hand-off — transforms + coefficients, 2,020 B per frame — on both sides and leave the dense J_regressor out:
+                # +0.8 %.)
+                alg = {"sweep_roles": B_MODEL_ALL + F * B_FRAME_ALL}
+            # HBM bytes per launch: rocprofv3 cannot run inside this process, so `traffic` is what the committed --pmc passes
+            # of THIS command measured (tools/profile_round.sh writes profiles/rN_xx_pmc_traffic.json: FETCH_SIZE doubled per the
+            # gfx950 note + WRITE_SIZE); `traffic_source` names that file.  Null when no committed pass matches the workload
+            # and size, or its kernel names are not the ones this build launches.
+            pm = pm_src = None
+            try:
+                import glob
+                pm_src = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_traffic.json")))[-1]
+                pm = json.load(open(pm_src))
+                if not (args.workload == pm["workload"] and F == pm["frames_per_gpu"]):
+                    pm = None
+            except Exception:
+                pm = None
+            kernels = {}
+            for k in alg:
+                # one launch per step (and no reduce launch): the launch period of the step's events IS this kernel's
+                dur = period_ms if (fused and not with_reduce) else prof[k]
+                a = alg[k] / (dur * 1e-3) / 1e9
+                ko = alg[k] / (prof[k] * 1e-3) / 1e9
+                kernels[k] = {"achieved": a, "frac": a / HBM_PEAK_GBS, "frac_of_measured_copy_rate": a / HBM_COPY_GBS,
+                              "algorithmic_bytes_per_launch": alg[k], "avg_launch_ms": dur,
+                              "avg_launch_ms_definition": ("launch period: two HIP events around %d back-to-back launches on the launch "
+                                                           "stream" % n_ev) if dur is period_ms else "dispatch begin -> end (HIP events)",
+                              "kernel_only": {"avg_launch_ms": prof[k], "achieved": ko, "frac": ko / HBM_PEAK_GBS,
+                                              "definition": "the dispatch's own begin -> end timestamps (hipExtLaunchKernelGGL events), "
+                                                            "without the dependent-launch boundary"},
+                              "traffic": pm["kernels"].get(pmc_name[k], {}).get("hbm_bytes") if pm else None}
+            # matrix-pipe view of the mesh kernel: the blend contraction is 2 x 20670 x 217 flop per frame; it is
+            # executed as three bf16 products per k-step on v_mfma_f32_32x32x16_bf16 (216 tiles x 14 k-steps x 9 MFMAs per 32 frames)
+            alg_flop = 2.0 * 20670 * 217 * F
+            exe_flop = 216 * ((F + 31) // 32) * 14 * 9 * 2.0 * 32 * 32 * 16
+            mk = "sweep_roles" if fused else "mesh_blend_lbs"
+            kernels[mk]["mfma"] = {
+                "algorithmic_TFLOPs": alg_flop / (prof[mk] * 1e-3) / 1e12, "f32_mfma_peak_TFLOPs": 157.3,
+                "executed_bf16_TFLOPs": exe_flop / (prof[mk] * 1e-3) / 1e12, "bf16_dense_peak_TFLOPs": 2500.0}
+            dom = max(alg, key=lambda k: prof[k])
+            bytes_launch, ach, traffic = alg[dom], kernels[dom]["achieved"], kernels[dom]["traffic"]
+            out["roofline"] = {
+                "bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS, "frac_of_measured_copy_rate": ach / HBM_COPY_GBS, "traffic": traffic,
+                "traffic_source": (os.path.relpath(pm_src, ROOT) + " (rocprofv3 --pmc passes of this command, "
+                                   "committed; not measured in this run)") if pm else None,
+                "algorithmic_bytes_per_launch": bytes_launch, "avg_launch_ms": kernels[dom]["avg_launch_ms"],
+                "avg_launch_ms_definition": kernels[dom]["avg_launch_ms_definition"],
+                "kernel_only": kernels[dom]["kernel_only"],
+                "algorithmic_bytes_definition": ("SURVEY.md 8d: B(F) = 19,347,120 (f32 model tensors, read once per launch) + "
+                                                 "F x 118,588 (params, keypoints, r, J, posed vertices)") if fused else
+                                                "per kernel: the model tensors it reads + its per-frame inputs and outputs",
+                "kernels": kernels}
+            out["kernel_ms"] = prof
+            if strong is not None:
+                out["c5_strong"] = strong
+            if world == 1:
+                # the rate a kept ceres::Solve would see: host parameters up, one sweep, residuals + Jacobian down (page-locked
+                # mirrors, the problem's own stream); never `value`
+                # (cache_sweep: what bodyfit_ceres::SweepCallback::PrepareForEvaluation does — the sweep stays in the problem's
+                #  page-locked cache for the blocks' Evaluate calls, the Jacobian goes down as its non-zero column blocks;
+                #  ..._dense: the same with the dense [2K][86] panel copied out into the caller's numpy arrays)
+                for _ in range(3):
+                    prob.cache_sweep(params_h, beta_h)
+                t1 = time.perf_counter()
+                for _ in range(50):
+                    prob.cache_sweep(params_h, beta_h)
+                out["pcie_inclusive_evals_per_s"] = F * 50 / (time.perf_counter() - t1)
+                for _ in range(3):
+                    prob.evaluate(params_h, beta_h, True)
+                t1 = time.perf_counter()
+                for _ in range(20):
+                    prob.evaluate(params_h, beta_h, True)
+                out["pcie_inclusive_dense_evals_per_s"] = F * 20 / (time.perf_counter() - t1)
+                if args.workload == "c3" and not args.no_ceres_path:
+                    out["ceres_path"] = ceres_path(synth, model, seq, F, evals_s)
+            if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed at N = 1 only
+                n_cpu = args.cpu_sample_frames or min(F, 256)
+                cseq = seq if args.workload == "c3" else synth.make_sequence(model, n_cpu, seed=0)
+                out["cpu_baseline"] = cpu_baseline(synth, model, cseq, n_cpu, (w, mu, cov) if args.workload == "c3" else None,
+                                                   beta_pose=20.0 if args.workload == "c3" else 5.0,
+                                                   beta_shape=30.0 if args.workload == "c3" else 0.0)
+            if not args.no_fit and world == 1 and args.workload == "c3":
+                # the second half of BASELINE.json's metric: frames/sec to convergence of the product's LM on c2 / c3 / c4
+                # (tools/fit_bench.py; reference hooks src/main_single_frame.cpp:234-249,265-269), and the checker's own fits
+                # (oracle evaluator under the dense numpy LM) on a bounded sample beside them
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import fit_bench
+                # every record: median of its repeats, final robustified cost per stage, launches and microseconds per LM iteration;
+                # c4 and c5_staged both go through drivers.run_multi (the reference's staging incl. the write-back after every
+                # solve); c5_window is configs[4] as ONE 1024-frame window (what --workload c5 --fit shards over the ranks)
+                fit = {"unit": "frames/s", "c2": fit_bench.fit_c2(api, synth, model, gm),
+                       "c3": fit_bench.fit_c3(api, synth, model, gm), "c4": fit_bench.fit_c4(api, synth, model, gm),
+                       "window_20": fit_bench.fit_window(api, synth, model, gm, 20, 60),
+                       "c5_staged": fit_bench.fit_c5(api, synth, model, gm), "c5_window": fit_bench.fit_c5_window(api, synth, model, gm)}
+                if not args.no_cpu_baseline:
+                    # eight threads: what the reference itself configures (options.num_threads = 8, include/MultiFrameBA.h:148;
+                    # 4 in include/Sim3BA.h:476) — and what these small problems can use: 25 to 500 residual blocks per evaluation
+                    # on all 256 hardware threads of the box is ten times SLOWER (fork/join of the OpenMP pool per evaluation)
+                    fit["cpu_baseline"] = fit_bench.cpu_fit_baseline(synth, model, threads=min(8, os.cpu_count() or 8))
+                out["fit"] = fit
         print(json.dumps(out), file=RECORD_OUT, flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +22,7 @@ def _last_json(out):
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"], cwd=ROOT,
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full"], cwd=ROOT,
                          capture_output=True, text=True, timeout=300)
     assert len([l for l in out.stdout.splitlines() if l.strip()]) == 1, out.stdout[:600]   # ONE line (RCCL's banner goes to stderr)
     d = _last_json(out.stdout)
@@ -61,6 +62,44 @@ def test_bench_single_gpu_line():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_outputs(tmp_path, synth, model, omodel):
+    """The plain run (no --full): the headline keys, exactly --steps timed steps in ONE bracket and nothing measured beside it;
+    --dump-outputs writes what the last timed step computed, float32 / float64 and at most 64 MB, the same in two runs, and
+    its reprojection rows are the checker's at the bench's inputs."""
+    runs = []
+    for i in range(2):
+        d_out = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "50", "--warmup", "5", "--dump-outputs",
+                              str(d_out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert len([l for l in out.stdout.splitlines() if l.strip()]) == 1, out.stdout[:600]
+        d = _last_json(out.stdout)
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+        assert d["unit"] == "evals/s" and d["higher_is_better"] is True and d["steps"] == 50 and d["full"] is False
+        assert abs(d["value"] - d["config"]["frames_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert d["timing"]["repeats"] == 1 and d["timing"]["ms_per_step_all"] == [d["ms_per_step"]] and d["sweep_timeouts"] == 0
+        assert not {"roofline", "kernel_ms", "c5_strong", "fit", "cpu_baseline", "ceres_path"} & set(d)
+        files = sorted(p.name for p in d_out.iterdir())
+        assert files == ["cloud.npy", "gmm_comp.npy", "jacobian.npy", "joints.npy", "residuals.npy"], files
+        assert sum(p.stat().st_size for p in d_out.iterdir()) <= 64 * 10**6
+        arrs = {f[:-4]: np.load(d_out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        runs.append(arrs)
+    for k in runs[0]:
+        assert runs[0][k].shape == runs[1][k].shape
+        assert np.allclose(runs[0][k], runs[1][k], rtol=1e-12, atol=1e-12 if runs[0][k].dtype == np.float64 else 1e-6), k
+    # the bench's inputs (bench.py, workload c3 on rank 0) through the checker
+    F = 256
+    seq = synth.make_sequence(model, F, seed=0)
+    x, beta = seq.gt_params + 0.01, np.tile(seq.gt_beta, (F, 1)) + 0.01
+    ro, Jo = omodel.evaluate_batch(seq, x, beta, 86, True, True, mode=0)
+    r, J = runs[0]["residuals"], runs[0]["jacobian"]
+    assert np.abs(r[:len(ro)] - ro).max() < 1e-9
+    assert J.shape == Jo.shape and np.abs(J - Jo).max() <= 1e-9 * max(1.0, np.abs(Jo).max())
+    assert runs[0]["cloud"].shape == (F, model.n_verts, 3) and runs[0]["joints"].shape == (F, 24, 3)
+
+
+@pytest.mark.gpu
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher (no WORLD_SIZE): bench.py starts its ranks itself as a child torch.distributed.run
     and relays rank 0's line — the form a driver that just runs `bench.py --gpus N` gets.  Rehearsed with both ranks on cuda:0
@@ -69,7 +108,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_SHARE_DEVICE0="1", BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--window", "64",
-                          "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                                   # ONE JSON line on stdout, whatever the ranks printed
@@ -92,7 +131,7 @@ def test_bench_two_ranks_rehearsal(workload, scaling):
     env = dict(os.environ, BENCH_SHARE_DEVICE0="1", BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "2", "--workload", workload,
-           "--no-cpu-baseline"] + (["--window", "128"] if workload == "c5" else [])
+           "--no-cpu-baseline", "--full"] + (["--window", "128"] if workload == "c5" else [])
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
@@ -104,7 +143,7 @@ def test_bench_two_ranks_rehearsal(workload, scaling):
 def test_bench_c5_fit_line(world):
     """--workload c5 --fit: a step is one complete fit of the window; N = 2 rehearsed with both ranks on cuda:0 over gloo."""
     env = dict(os.environ, BENCH_SHARE_DEVICE0="1", BENCH_BACKEND="gloo")
-    base = ["bench.py", "--gpus", str(world), "--workload", "c5", "--fit", "--window", "64", "--steps", "2", "--warmup", "1"]
+    base = ["bench.py", "--gpus", str(world), "--workload", "c5", "--fit", "--window", "64", "--steps", "2", "--warmup", "1", "--full"]
     if world == 1:
         cmd = [sys.executable] + base
     else:

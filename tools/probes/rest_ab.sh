@@ -1,7 +1,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for rnd in 1 2 3; do
 for r in 0 0.3 1 2 3 6; do
-  timeout -k 10 120 python bench.py --steps 20 --warmup 5 --prewarm-rest-ms $r --no-cpu-baseline --no-fit --no-c5-strong --no-ceres-path > /tmp/b.json 2>/dev/null
+  timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --prewarm-rest-ms $r --no-cpu-baseline --no-fit --no-c5-strong --no-ceres-path > /tmp/b.json 2>/dev/null
   python - <<PY
 import json
 d=json.load(open("/tmp/b.json")); t=d["timing"]

@@ -1,5 +1,5 @@
 """Digest gpurun_out/prof_<tag>/ (tools/profile_round.sh) into the small files kept under profiles/:
-  <tag>_kernel_stats.csv     rocprofv3 --stats kernel table of the default bench.py run
+  <tag>_kernel_stats.csv     rocprofv3 --stats kernel table of the bench.py --full run
   <tag>_bench.json           the bench line printed by that run
   <tag>_kernel_stats_post_prewarm.json   the sweep kernel's launch durations behind the cold bracket and the prewarm sweeps
   <tag>_pmc_traffic.json     HBM bytes per launch and kernel from the FETCH_SIZE / WRITE_SIZE passes"""
@@ -43,7 +43,7 @@ if tr:
         q = lambda f: d[min(len(d) - 1, int(f * len(d)))]
         post[k] = {"launches": len(d), "skipped_leading_launches": skip if len(d) != len(v) else 0, "avg_ns": round(sum(d) / len(d), 1),
                    "median_ns": q(0.5), "p10_ns": q(0.1), "p90_ns": q(0.9), "min_ns": d[0], "max_ns": d[-1]}
-    json.dump({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-fit --no-ceres-path --no-c5-strong (the kernel "
+    json.dump({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-fit --no-ceres-path --no-c5-strong (the kernel "
                          "trace of the same run as <tag>_kernel_stats.csv), durations = End - Start per dispatch, dispatch order",
                "note": "sweep kernels: the first warmup + steps + prewarm_steps launches (cold bracket, untimed prewarm) are dropped; "
                        "what remains are the timed brackets' launches and the in-bench HIP-event sample behind them",
@@ -63,7 +63,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
 for k, d in kern.items():
     d["hbm_bytes"] = int((2 * d.get("FETCH_SIZE_KiB", 0.0) + d.get("WRITE_SIZE_KiB", 0.0)) * 1024)
 out = {
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 2",
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2",
     "workload": "c3", "frames_per_gpu": bench["config"]["frames_per_gpu"],
     "units": "FETCH_SIZE / WRITE_SIZE in KiB per launch (average over launches); hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
              "(gfx950: FETCH_SIZE reports half the bytes of wide coalesced reads, MI355X_MICROARCH.md HBM section)",
@@ -88,6 +88,6 @@ if sq:
             d["mfma_busy_over_sq_busy"] = round(d["SQ_VALU_MFMA_BUSY_CYCLES"] / d["SQ_BUSY_CYCLES"], 4)
         if d.get("SQ_LDS_IDX_ACTIVE") and "SQ_LDS_BANK_CONFLICT" in d:
             d["lds_conflict_share"] = round(d["SQ_LDS_BANK_CONFLICT"] / d["SQ_LDS_IDX_ACTIVE"], 4)
-    json.dump({"source": "rocprofv3 --pmc <three SQ counters per pass> -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 2",
+    json.dump({"source": "rocprofv3 --pmc <three SQ counters per pass> -- python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2",
                "note": "sums over all shader engines / CUs per launch, as rocprofv3 reports them", "kernels": sq},
               open(f"profiles/{tag}_pmc_sq.json", "w"), indent=1)
