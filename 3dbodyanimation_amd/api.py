@@ -194,6 +194,10 @@ def load_library():
     lib.bodyfit_last_exchange_count.argtypes = [C.c_void_p]
     lib.bodyfit_last_exchange_count.restype = C.c_long
     lib.bodyfit_forward.argtypes = [C.c_void_p, _dp, _dp, _dp, _fp]
+    lib.bodyfit_forward_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_forward_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_forward_vjp.argtypes = [C.c_void_p, _dp, _dp, _fp, _dp, _dp, _dp]
     lib.bodyfit_writeback_batch.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _dp]
     lib.bodyfit_evaluate_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_dp), _dp, C.POINTER(_dp)]
     _u8p = C.POINTER(C.c_uint8)
@@ -373,6 +377,7 @@ class Problem:
         _check(lib.bodyfit_problem_layout(self.h, C.byref(self.layout)))
         self.n_cols = n_cols
         self.want_mesh = want_mesh
+        self.beta_per_frame = bool(beta_per_frame)
         self.n_param_rows = self.n_frames + (1 if temporal_halo else 0)
 
     @classmethod
@@ -436,6 +441,40 @@ class Problem:
         _check(load_library().bodyfit_forward(self.h, _d(x), _d(b), _d(joints),
                                               cloud.ctypes.data_as(_fp) if cloud is not None else None))
         return joints, cloud
+
+    def forward_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_joints_ptr: int | None, d_cloud_ptr: int | None,
+                       cloud_row_floats: int | None = None, stream: int | None = None):
+        """bodyfit_forward_device: the two-launch forward into device memory, asynchronous on `stream`."""
+        rf = 3 * self.model.n_verts if cloud_row_floats is None else int(cloud_row_floats)
+        _check(load_library().bodyfit_forward_device(self.h, d_params_ptr, d_beta_ptr, d_joints_ptr, d_cloud_ptr, rf, stream))
+
+    def forward_vjp(self, frame_params, beta=None, grad_cloud=None, grad_joints=None):
+        """dL/dframe_params [F(+1), 76] and dL/dbeta ([nS] shared, [F, nS] per frame; None when n_cols == 76) of the forward,
+        given dL/dcloud [F, V, 3] and / or dL/djoints [F, 24, 3] (bodyfit_forward_vjp)."""
+        x = _c64(frame_params); b = _c64(beta) if beta is not None else None
+        assert x.size == self.n_param_rows * N_FRAME_PARAMS, "frame_params must be [F(+1), 76]"
+        G = None if grad_cloud is None else np.ascontiguousarray(grad_cloud, dtype=np.float32)
+        H = None if grad_joints is None else _c64(grad_joints)
+        if G is not None:
+            assert G.size == self.n_frames * self.model.n_verts * 3, "grad_cloud must be [F, V, 3]"
+        if H is not None:
+            assert H.size == self.n_frames * self.model.n_joints * 3, "grad_joints must be [F, nJ, 3]"
+        gx = np.empty((self.n_param_rows, N_FRAME_PARAMS))
+        has_beta = self.n_cols > N_FRAME_PARAMS
+        gb = None
+        if has_beta:
+            gb = np.empty((self.n_frames, self.model.n_shape)) if self.beta_per_frame else np.empty(self.model.n_shape)
+        _check(load_library().bodyfit_forward_vjp(self.h, _d(x), _d(b), G.ctypes.data_as(_fp) if G is not None else None,
+                                                  _d(H), _d(gx), _d(gb)))
+        return gx, gb
+
+    def forward_vjp_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_grad_cloud_ptr: int | None,
+                           d_grad_joints_ptr: int | None, d_grad_params_ptr: int, d_grad_beta_ptr: int | None,
+                           grad_cloud_row_floats: int | None = None, stream: int | None = None):
+        """bodyfit_forward_vjp_device: asynchronous on `stream`, device pointers throughout."""
+        rf = 3 * self.model.n_verts if grad_cloud_row_floats is None else int(grad_cloud_row_floats)
+        _check(load_library().bodyfit_forward_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_cloud_ptr, rf,
+                                                         d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr, stream))
 
     def writeback(self, frame_params, beta=None, want_cloud=False):
         """The reference's post-solve write-back for every frame, on the device (bodyfit_writeback_batch):

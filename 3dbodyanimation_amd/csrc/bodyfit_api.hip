@@ -164,6 +164,17 @@ struct bodyfit_model {
   std::vector<int> parent;
   std::vector<double> J0, S, offset;
   Allocs mem;
+  // forward VJP (k_forward_vjp.hip), built on the model's first VJP and freed with the model: the operand block transposed
+  // for the blend gradient, and every joint's skinning list (vertex ascending, f32 weights as the forward skins with them)
+  std::vector<uint32_t> h_wIdx;
+  std::vector<float> h_wVal;
+  mutable std::mutex vjp_mu;
+  mutable bool vjp_ready = false;
+  mutable uint16_t* d_dirsT = nullptr;
+  mutable int* d_csr_off = nullptr;
+  mutable int* d_csr_v = nullptr;
+  mutable float* d_csr_w = nullptr;
+  mutable Allocs vjp_mem;
 };
 
 struct bodyfit_gmm {
@@ -242,6 +253,17 @@ struct bodyfit_problem {
   Pinned<int> c_comp;
   size_t c_npar = 0, c_nbeta = 0;       // valid entries of c_params / c_beta
   hipStream_t copy_stream = nullptr;   // the Ceres-kept path's own stream (H2D, sweep, D2H)
+  // forward VJP buffers, allocated on the problem's first VJP (bodyfit_forward_vjp_device): its own mesh operands (so an
+  // evaluation's views are left alone), the vertex gradients gb, blended vertices, blend partials, transform gradients
+  bool vjp_alloc = false, vjp_mesh_alloc = false;
+  MeshCoef vjp_mc{};
+  double* vjp_r = nullptr;
+  double* vjp_joints = nullptr;
+  double* vjp_gbf = nullptr;           // [F][nS] per-frame beta gradients
+  float* vjp_gb = nullptr;
+  float* vjp_bbuf = nullptr;
+  float* vjp_part = nullptr;
+  double* vjp_dT = nullptr;
   Allocs mem;
 };
 
@@ -726,6 +748,8 @@ int bodyfit_model_create(const bodyfit_model_desc* desc, int device, bodyfit_mod
     HIP_TRY(m->mem.upload(&d.vtB, vtB));
     HIP_TRY(m->mem.upload(&d.wIdx, wIdx));
     HIP_TRY(m->mem.upload(&d.wVal, wVal));
+    m->h_wIdx = std::move(wIdx);
+    m->h_wVal = std::move(wVal);
   }
   *out = guard.release();
   return BODYFIT_OK;
@@ -2045,6 +2069,184 @@ int bodyfit_forward(bodyfit_problem* p, const double* frame_params, const double
     if (attempt == 0 && fused_timed_out(p)) continue;
     break;
   }
+  return BODYFIT_OK;
+}
+
+int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, double* d_joints,
+                           float* d_cloud, long long cloud_row_floats, void* stream) {
+  if (!p || !d_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  if (d_cloud && !p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "problem was created without want_mesh");
+  if (d_cloud && cloud_row_floats < 3LL * m->V) return fail(BODYFIT_ERR_INVALID, "cloud_row_floats < 3 V");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  p->async_stream = st;
+  p->async_pending = true;
+  const int npose = 7 + 3 * (m->nJ - 1);
+  const double* d_b = p->lay.n_cols > npose ? d_beta : nullptr;
+  // the two-launch sweep without Jacobian or priors: joints straight into the caller's buffer, the cloud through the problem's
+  // padded one
+  const PriorArgs none{};
+  launch_frame_resjac(m->d, p->d, d_frame_params, d_b, p->d_r, nullptr, d_joints ? d_joints : p->d_joints,
+                      d_cloud ? p->mc : MeshCoef{}, 0, none, st);
+  if (d_cloud) {
+    launch_mesh(m->d, p->d, p->mc, p->d_cloud, none, d_frame_params, st);
+    const size_t row = (size_t)m->V * 3 * sizeof(float), pitch = (size_t)m->d.nVTiles * kVTile * 3 * sizeof(float);
+    HIP_TRY(hipMemcpy2DAsync(d_cloud, (size_t)cloud_row_floats * sizeof(float), p->d_cloud, pitch, row, (size_t)p->d.F,
+                             hipMemcpyDeviceToDevice, st));
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return BODYFIT_OK;
+}
+
+namespace {
+
+// the model's VJP operands, once (first VJP of the model): transposed operand block, per-joint skinning lists
+int vjp_model_ready(const bodyfit_model* m, hipStream_t st) {
+  std::lock_guard<std::mutex> lock(m->vjp_mu);
+  if (m->vjp_ready) return BODYFIT_OK;
+  const int nVT = m->d.nVTiles, nJ = m->nJ;
+  std::vector<std::vector<std::pair<int, float>>> lists(nJ);
+  for (int vt = 0; vt < nVT; ++vt)
+    for (int col = 0; col < kVTile; ++col) {
+      const int v = vt * kVTile + col;
+      if (v >= m->V) continue;
+      for (int i = 0; i < kMeshNnz; ++i) {
+        const float w = m->h_wVal[((size_t)vt * kVTile + col) * kMeshNnz + i];
+        const int j = (int)((m->h_wIdx[(size_t)vt * kVTile + col] >> (8 * i)) & 0xffu);
+        if (w != 0.0f && j < nJ) lists[j].push_back({v, w});
+      }
+    }
+  std::vector<int> off(kMaxJoints + 1, 0), vid;
+  std::vector<float> wv;
+  for (int j = 0; j < kMaxJoints; ++j) {
+    if (j < nJ) {
+      std::sort(lists[j].begin(), lists[j].end(), [](const std::pair<int, float>& a, const std::pair<int, float>& b) {
+        return a.first < b.first;
+      });
+      for (const auto& e : lists[j]) { vid.push_back(e.first); wv.push_back(e.second); }
+    }
+    off[j + 1] = (int)vid.size();
+  }
+  HIP_TRY(m->vjp_mem.alloc(&m->d_dirsT, vjp_dirs_t_elems(nVT)));
+  const int* d_off = nullptr;
+  const int* d_v = nullptr;
+  const float* d_w = nullptr;
+  HIP_TRY(m->vjp_mem.upload(&d_off, off));
+  HIP_TRY(m->vjp_mem.upload(&d_v, vid));
+  HIP_TRY(m->vjp_mem.upload(&d_w, wv));
+  m->d_csr_off = const_cast<int*>(d_off);
+  m->d_csr_v = const_cast<int*>(d_v);
+  m->d_csr_w = const_cast<float*>(d_w);
+  launch_vjp_build_dirs_t(m->d, m->d_dirsT, st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // (once per model: VJPs on other streams read the block too)
+  m->vjp_ready = true;
+  return BODYFIT_OK;
+}
+
+int vjp_problem_ready(bodyfit_problem* p, bool mesh) {
+  const bodyfit_model* m = p->m;
+  const int F = p->d.F, nFT = p->d.nFTiles, nVT = m->d.nVTiles;
+  if (!p->vjp_alloc) {
+    HIP_TRY(p->mem.alloc(&p->vjp_gbf, (size_t)F * std::max(m->nS, 1)));
+    p->vjp_alloc = true;
+  }
+  if (mesh && !p->vjp_mesh_alloc) {
+    const size_t nfa = (size_t)nFT * kBlendKSteps * 2 * 64 * 8, nsk = (size_t)nFT * kFTile * m->nJ * 12;
+    HIP_TRY(p->mem.alloc(&p->vjp_mc.featA, nfa));
+    HIP_TRY(p->mem.alloc(&p->vjp_mc.skinT, nsk));
+    HIP_TRY(hipMemset(p->vjp_mc.featA, 0, nfa * sizeof(uint16_t)));
+    HIP_TRY(hipMemset(p->vjp_mc.skinT, 0, nsk * sizeof(float)));
+    HIP_TRY(p->mem.alloc(&p->vjp_r, (size_t)std::max(1, p->lay.reproj_rows)));
+    HIP_TRY(p->mem.alloc(&p->vjp_joints, (size_t)F * m->nJ * 3));
+    HIP_TRY(p->mem.alloc(&p->vjp_gb, vjp_gb_elems(nFT, nVT)));
+    HIP_TRY(p->mem.alloc(&p->vjp_bbuf, (size_t)F * nVT * kVTile * 3));
+    HIP_TRY(p->mem.alloc(&p->vjp_part, vjp_part_elems(nFT, nVT)));
+    HIP_TRY(p->mem.alloc(&p->vjp_dT, (size_t)F * kMaxJoints * 12));
+    p->vjp_mesh_alloc = true;
+  }
+  return BODYFIT_OK;
+}
+
+}  // namespace
+
+int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                               const float* d_grad_cloud, long long grad_cloud_row_floats, const double* d_grad_joints,
+                               double* d_grad_frame_params, double* d_grad_beta, void* stream) {
+  if (!p || !d_frame_params || !d_grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const int npose = 7 + 3 * (m->nJ - 1), F = p->d.F, nS = m->nS;
+  const bool has_beta = p->lay.n_cols > npose;
+  if (d_grad_cloud && !p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "grad_cloud needs a problem created with want_mesh");
+  if (d_grad_cloud && grad_cloud_row_floats < 3LL * m->V) return fail(BODYFIT_ERR_INVALID, "grad_cloud_row_floats < 3 V");
+  if (has_beta && !d_grad_beta) return fail(BODYFIT_ERR_INVALID, "grad_beta is required when n_cols = 76 + n_shape");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const double* d_b = has_beta ? d_beta : nullptr;
+  const bool mesh = d_grad_cloud != nullptr;
+  if (mesh)
+    if (int rc = vjp_model_ready(m, st)) return rc;
+  if (int rc = vjp_problem_ready(p, mesh)) return rc;
+  p->async_stream = st;
+  p->async_pending = true;
+  if (mesh) {
+    const PriorArgs none{};
+    launch_frame_resjac(m->d, p->d, d_frame_params, d_b, p->vjp_r, nullptr, p->vjp_joints, p->vjp_mc, 0, none, st);
+    launch_vjp_mesh(m->d, p->d, p->vjp_mc, d_grad_cloud, grad_cloud_row_floats, p->vjp_gb, p->vjp_bbuf, st);
+    launch_vjp_blend_t(m->d, p->d, p->vjp_gb, m->d_dirsT, p->vjp_part, st);
+    launch_vjp_skin_t(m->d, p->d, m->d_csr_off, m->d_csr_v, m->d_csr_w, d_grad_cloud, grad_cloud_row_floats, p->vjp_bbuf,
+                      p->vjp_dT, st);
+  }
+  const bool per_frame = p->desc.beta_per_frame != 0;
+  double* gbf = (d_grad_beta && per_frame) ? d_grad_beta : p->vjp_gbf;
+  launch_vjp_chain(m->d, p->d, d_frame_params, d_b, mesh ? p->vjp_dT : nullptr, mesh ? p->vjp_part : nullptr, d_grad_joints,
+                   d_grad_frame_params, gbf, st);
+  if (d_grad_beta && !per_frame) launch_vjp_beta_sum(gbf, F, nS, d_grad_beta, st);
+  if (p->n_param_rows > F)   // the halo row
+    HIP_TRY(hipMemsetAsync(d_grad_frame_params + (size_t)F * kFrameParams, 0,
+                           (size_t)(p->n_param_rows - F) * kFrameParams * sizeof(double), st));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return BODYFIT_OK;
+}
+
+int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* grad_cloud,
+                        const double* grad_joints, double* grad_frame_params, double* grad_beta) {
+  if (!p || !frame_params || !grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const int npose = 7 + 3 * (m->nJ - 1), F = p->d.F, nS = m->nS;
+  const bool has_beta = p->lay.n_cols > npose;
+  if (grad_cloud && !p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "grad_cloud needs a problem created with want_mesh");
+  if (has_beta && !grad_beta) return fail(BODYFIT_ERR_INVALID, "grad_beta is required when n_cols = 76 + n_shape");
+  HIP_TRY(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> lock(p->mu);
+  if (int ro = order_after_async(p, nullptr)) return ro;
+  const size_t npar = (size_t)p->n_param_rows * npose;
+  const size_t nbeta = (has_beta && beta) ? (size_t)(p->desc.beta_per_frame ? F * nS : nS) : 0;
+  const size_t ngb = grad_beta ? (size_t)std::max(1, p->desc.beta_per_frame ? F * nS : nS) : 0;
+  const size_t ncl = grad_cloud ? (size_t)F * m->V * 3 : 0, njt = grad_joints ? (size_t)F * m->nJ * 3 : 0;
+  // one temporary block: parameters, beta, upstream gradients, outputs
+  Allocs tmp;
+  double *d_x = nullptr, *d_b = nullptr, *d_gx = nullptr, *d_gb = nullptr, *d_H = nullptr;
+  float* d_G = nullptr;
+  HIP_TRY(tmp.alloc(&d_x, npar));
+  HIP_TRY(tmp.alloc(&d_gx, npar));
+  if (nbeta) HIP_TRY(tmp.alloc(&d_b, nbeta));
+  if (ngb) HIP_TRY(tmp.alloc(&d_gb, ngb));
+  if (ncl) HIP_TRY(tmp.alloc(&d_G, ncl));
+  if (njt) HIP_TRY(tmp.alloc(&d_H, njt));
+  HIP_TRY(hipMemcpy(d_x, frame_params, npar * sizeof(double), hipMemcpyHostToDevice));
+  if (nbeta) HIP_TRY(hipMemcpy(d_b, beta, nbeta * sizeof(double), hipMemcpyHostToDevice));
+  if (ncl) HIP_TRY(hipMemcpy(d_G, grad_cloud, ncl * sizeof(float), hipMemcpyHostToDevice));
+  if (njt) HIP_TRY(hipMemcpy(d_H, grad_joints, njt * sizeof(double), hipMemcpyHostToDevice));
+  if (ngb) HIP_TRY(hipMemset(d_gb, 0, ngb * sizeof(double)));
+  if (int rc = bodyfit_forward_vjp_device(p, d_x, d_b, d_G, 3LL * m->V, d_H, d_gx, d_gb, nullptr)) return rc;
+  p->async_pending = false;   // (NULL stream, waited for below)
+  HIP_TRY(hipMemcpy(grad_frame_params, d_gx, npar * sizeof(double), hipMemcpyDeviceToHost));
+  if (ngb) HIP_TRY(hipMemcpy(grad_beta, d_gb, ngb * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
   return BODYFIT_OK;
 }
 

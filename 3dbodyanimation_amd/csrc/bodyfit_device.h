@@ -353,4 +353,20 @@ void launch_mean_pixel_error(int F, int nJ, const int* d_kp_offset, const int* d
                              const double* d_joints, double fx, double fy, double cx, double cy, double* d_out, hipStream_t s);
 void launch_regress(int nJ, int V, int ncol, const double* d_reg, const double* d_x, double* d_out, hipStream_t s);
 
+// reverse-mode gradient of the forward (k_forward_vjp.hip; bodyfit_forward_vjp_device)
+size_t vjp_dirs_t_elems(int nVT);            // bf16 entries of the transposed operand block (per model, built on first use)
+size_t vjp_gb_elems(int nFT, int nVT);       // f32 entries of the blended-vertex gradients gb (per problem)
+int vjp_n_chunks(int nVT);                   // vertex-tile chunks of the blend transpose
+size_t vjp_part_elems(int nFT, int nVT);     // f32 entries of its per-chunk partials
+void launch_vjp_build_dirs_t(const DevModel& M, uint16_t* d_dirsT, hipStream_t s);
+void launch_vjp_mesh(const DevModel& M, const DevProblem& P, const MeshCoef& mc, const float* d_G, long long row_floats,
+                     float* d_gb, float* d_bbuf, hipStream_t s);
+void launch_vjp_blend_t(const DevModel& M, const DevProblem& P, const float* d_gb, const uint16_t* d_dirsT, float* d_part,
+                        hipStream_t s);
+void launch_vjp_skin_t(const DevModel& M, const DevProblem& P, const int* d_csr_off, const int* d_csr_v, const float* d_csr_w,
+                       const float* d_G, long long row_floats, const float* d_bbuf, double* d_dT, hipStream_t s);
+void launch_vjp_chain(const DevModel& M, const DevProblem& P, const double* d_params, const double* d_beta, const double* d_dT,
+                      const float* d_part, const double* d_H, double* d_gx, double* d_gbeta_frames, hipStream_t s);
+void launch_vjp_beta_sum(const double* d_gbeta_frames, int F, int nS, double* d_out, hipStream_t s);
+
 }  // namespace bodyfit

@@ -244,6 +244,36 @@ int bodyfit_evaluate_block_cached(bodyfit_problem* p, int kind, int index, const
 int bodyfit_forward(bodyfit_problem* p, const double* frame_params, const double* beta,
                     double* joints, float* cloud);
 
+/* Device-pointer form of bodyfit_forward into caller memory, asynchronous on `stream` (no host synchronisation):
+ *   d_frame_params [F(+1)][76], d_beta [nS] or [F][nS] (NULL: beta = 0), d_joints [F][nJ][3] f64 or NULL,
+ *   d_cloud [F][cloud_row_floats] f32 (cloud_row_floats >= 3 V; needs want_mesh) or NULL.
+ * Always the two-launch sweep (k_frame_resjac, then k_mesh_blend_lbs: no in-launch waits, so no bodyfit_sweep_status
+ * round trip), which is the sweep bodyfit_forward_vjp* differentiates: its cloud is bodyfit_forward's with the one-launch
+ * sweep switched off (BODYFIT_ONE_LAUNCH=0) bit for bit, and within 2e-6 of the one-launch sweep's.  Ordered like
+ * bodyfit_evaluate_device (it uses the problem's sweep buffers).                                                      */
+int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, double* d_joints,
+                           float* d_cloud, long long cloud_row_floats, void* stream);
+
+/* Reverse-mode gradient (vector-Jacobian product) of that forward: given the upstream gradients
+ *   d_grad_cloud  [F][grad_cloud_row_floats] f32 = dL/dcloud (needs want_mesh) or NULL,
+ *   d_grad_joints [F][nJ][3] f64 = dL/djoints or NULL,
+ * writes d_grad_frame_params [F(+1)][76] f64 = dL/dframe_params (the halo row of a temporal_halo problem: 0) and
+ * d_grad_beta = dL/dbeta, [nS] summed over the frames when beta is shared, [F][nS] when beta_per_frame (required when
+ * n_cols = 76 + nS; with n_cols = 76 it may be NULL, otherwise it receives zeros; zeros too without use_shape).
+ * Under the problem's use_shape / pose_blend / beta_per_frame and its fixed R0.  Asynchronous on `stream`, ordered like
+ * bodyfit_evaluate_device; uses buffers of its own (allocated on the problem's first VJP, and the model's transposed
+ * operand block on the model's first VJP: that first call synchronises once), so it leaves the sweep buffers alone.
+ * Deterministic: no atomics, fixed summation orders; a frame's rows depend on that frame only (bit-identical whatever F).
+ * Without d_grad_cloud only the f64 chain kernel runs (problems without want_mesh included).
+ * BODYFIT_ERR_INVALID: NULL problem / parameters / d_grad_frame_params, grad_cloud without want_mesh or with a row
+ * shorter than 3 V, d_grad_beta missing with n_cols = 76 + nS.                                                          */
+int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                               const float* d_grad_cloud, long long grad_cloud_row_floats, const double* d_grad_joints,
+                               double* d_grad_frame_params, double* d_grad_beta, void* stream);
+/* Host-pointer form of bodyfit_forward_vjp_device (same shapes, grad_cloud rows of 3 V floats), synchronous. */
+int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* grad_cloud,
+                        const double* grad_joints, double* grad_frame_params, double* grad_beta);
+
 /* The post-solve write-back of a whole solve on the device: for every frame
  *   r[0] <- R(rootAA) r[0]  (left-multiplied, so it compounds over repeated solves),  p <- rootT,
  *   r[j] <- R(jointAA[j]),  Avatar::update()  (the Sim3 scale is dropped),
