@@ -379,6 +379,7 @@ class Problem:
         self.want_mesh = want_mesh
         self.beta_per_frame = bool(beta_per_frame)
         self.n_param_rows = self.n_frames + (1 if temporal_halo else 0)
+        self.n_frame_params = 7 + 3 * (model.n_joints - 1)   # 76 for SMPL's 24 joints
 
     @classmethod
     def from_sequence(cls, model: Model, seq, **kw):
@@ -387,7 +388,7 @@ class Problem:
     def evaluate(self, frame_params, beta=None, want_jacobian=True):
         L = self.layout
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
-        assert x.size == self.n_param_rows * N_FRAME_PARAMS, "frame_params must be [F(+1), 76]"
+        assert x.size == self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         r = np.empty(L.total_rows); comp = np.zeros(self.n_frames, np.int32)
         J = np.empty((L.reproj_rows, L.n_cols)) if want_jacobian else None
         _check(load_library().bodyfit_evaluate_batch(self.h, _d(x), _d(b), _d(r), _d(J), _i(comp), int(want_jacobian)))
@@ -436,6 +437,7 @@ class Problem:
 
     def forward(self, frame_params, beta=None, want_cloud=True):
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
+        assert x.size >= self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         joints = np.empty((self.n_frames, self.model.n_joints, 3))
         cloud = np.empty((self.n_frames, self.model.n_verts, 3), np.float32) if want_cloud else None
         _check(load_library().bodyfit_forward(self.h, _d(x), _d(b), _d(joints),
@@ -449,18 +451,18 @@ class Problem:
         _check(load_library().bodyfit_forward_device(self.h, d_params_ptr, d_beta_ptr, d_joints_ptr, d_cloud_ptr, rf, stream))
 
     def forward_vjp(self, frame_params, beta=None, grad_cloud=None, grad_joints=None):
-        """dL/dframe_params [F(+1), 76] and dL/dbeta ([nS] shared, [F, nS] per frame; None when n_cols == 76) of the forward,
-        given dL/dcloud [F, V, 3] and / or dL/djoints [F, 24, 3] (bodyfit_forward_vjp)."""
+        """dL/dframe_params [F(+1), 7 + 3 (nJ - 1)] (76 for 24 joints) and dL/dbeta ([nS] shared, [F, nS] per frame; None
+        without the shape block) of the forward, given dL/dcloud [F, V, 3] and / or dL/djoints [F, nJ, 3] (bodyfit_forward_vjp)."""
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
-        assert x.size == self.n_param_rows * N_FRAME_PARAMS, "frame_params must be [F(+1), 76]"
+        assert x.size == self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         G = None if grad_cloud is None else np.ascontiguousarray(grad_cloud, dtype=np.float32)
         H = None if grad_joints is None else _c64(grad_joints)
         if G is not None:
             assert G.size == self.n_frames * self.model.n_verts * 3, "grad_cloud must be [F, V, 3]"
         if H is not None:
             assert H.size == self.n_frames * self.model.n_joints * 3, "grad_joints must be [F, nJ, 3]"
-        gx = np.empty((self.n_param_rows, N_FRAME_PARAMS))
-        has_beta = self.n_cols > N_FRAME_PARAMS
+        gx = np.empty((self.n_param_rows, self.n_frame_params))
+        has_beta = self.n_cols > self.n_frame_params
         gb = None
         if has_beta:
             gb = np.empty((self.n_frames, self.model.n_shape)) if self.beta_per_frame else np.empty(self.model.n_shape)

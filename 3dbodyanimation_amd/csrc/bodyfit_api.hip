@@ -364,7 +364,7 @@ int sweep(bodyfit_problem* p, const double* d_params, const double* d_beta, int 
   if (!mesh) mc = MeshCoef{};
   const bodyfit_problem_desc& D = p->desc;
   PriorArgs pa{};
-  pa.F = p->d.F; pa.nS = m->nS; pa.beta_stride = p->d.beta_stride;
+  pa.F = p->d.F; pa.nS = m->nS; pa.beta_stride = p->d.beta_stride; pa.npose = 7 + 3 * (m->nJ - 1);
   pa.has_gmm = p->has_gmm ? 1 : 0;
   if (p->has_gmm) pa.g = p->gmm;
   pa.beta_pose = D.beta_pose;
@@ -459,6 +459,13 @@ int bodyfit_model_create(const bodyfit_model_desc* desc, int device, bodyfit_mod
   for (int j = 1; j < nJ; ++j)
     if (desc->parent[j] < 0 || desc->parent[j] >= j)
       return fail(BODYFIT_ERR_INVALID, "kintree must be topologically ordered with a single root");
+  {
+    // the frame role walks a joint's ancestors from a packed list of 12 entries (root excluded): depth <= 13
+    std::vector<int> depth(nJ, 0);
+    for (int j = 1; j < nJ; ++j)
+      if ((depth[j] = depth[desc->parent[j]] + 1) > kMaxDepth)
+        return fail(BODYFIT_ERR_INVALID, "kintree deeper than 13 levels below the root (the ancestor walk holds 12 joints)");
+  }
   for (int l = 0; l < nL; ++l)
     if (desc->landmark_vid[l] < 0 || desc->landmark_vid[l] >= V) return fail(BODYFIT_ERR_INVALID, "landmark vertex id");
   const int nReg = desc->n_kp_regressors;
@@ -547,11 +554,11 @@ int bodyfit_model_create(const bodyfit_model_desc* desc, int device, bodyfit_mod
   HIP_TRY(m->mem.upload(&d.level_off, level_off));
   HIP_TRY(m->mem.upload(&d.level_joint, level_joint));
   put(kTabAnc, anc.data(), anc.size() * sizeof(unsigned));
-  // the same ancestors as a packed walk list: nearest first, 5 bits each, 0-terminated (joint ids 1..23; depth <= 12)
+  // the same ancestors as a packed walk list: nearest first, 5 bits each, 0-terminated (joint ids 1..23; depth <= kMaxDepth)
   std::vector<unsigned long long> chain(nJ, 0ull);
   for (int j = 1; j < nJ; ++j) {
     int lvl = 0;
-    for (int k = m->parent[j]; k > 0 && lvl < 12; k = m->parent[k], ++lvl) chain[j] |= (unsigned long long)k << (5 * lvl);
+    for (int k = m->parent[j]; k > 0; k = m->parent[k], ++lvl) chain[j] |= (unsigned long long)k << (5 * lvl);   // (lvl < 12: kMaxDepth)
   }
   put(kTabChain, chain.data(), chain.size() * sizeof(unsigned long long));
   put(kTabOffset, m->offset.data(), m->offset.size() * sizeof(double));
@@ -870,6 +877,8 @@ int bodyfit_problem_create(const bodyfit_model* m, const bodyfit_problem_desc* d
   for (int k = 0; k < K; ++k)
     if (desc->kp_id[k] < 0 || desc->kp_id[k] >= nJ + m->nL + m->nReg) return fail(BODYFIT_ERR_INVALID, "keypoint id out of range");
   if (desc->gmm && desc->gmm->d.D != 3 * (nJ - 1)) return fail(BODYFIT_ERR_INVALID, "GMM dimension must be 3 (n_joints - 1)");
+  if (desc->beta_pose > 0.0 && nJ != kMaxJoints)
+    return fail(BODYFIT_ERR_INVALID, "the pose prior (beta_pose > 0) is built for 24 joints (69 pose dimensions)");
   if (desc->want_mesh && (size_t)((F + kFTile - 1) / kFTile) * kFTile * m->d.nVTiles * kVTile * 12 >= ((size_t)1 << 32))
     return fail(BODYFIT_ERR_INVALID, "mesh path: the cloud of one problem must stay below 4 GiB (split the frames)");
   if (desc->want_mesh && !m->mesh_ok)
@@ -2205,8 +2214,7 @@ int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params,
                    d_grad_frame_params, gbf, st);
   if (d_grad_beta && !per_frame) launch_vjp_beta_sum(gbf, F, nS, d_grad_beta, st);
   if (p->n_param_rows > F)   // the halo row
-    HIP_TRY(hipMemsetAsync(d_grad_frame_params + (size_t)F * kFrameParams, 0,
-                           (size_t)(p->n_param_rows - F) * kFrameParams * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(d_grad_frame_params + (size_t)F * npose, 0, (size_t)(p->n_param_rows - F) * npose * sizeof(double), st));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return BODYFIT_OK;

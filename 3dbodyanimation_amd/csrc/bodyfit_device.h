@@ -10,6 +10,8 @@ namespace bodyfit {
 
 constexpr int kMaxJoints = 24;     // SMPL
 constexpr int kMaxShape = 10;
+constexpr int kMaxDepth = 13;     // levels below the root: the packed ancestor walk list holds 12 joints (5 bits x 12)
+static_assert(kMaxJoints <= 32 && 5 * (kMaxDepth - 1) <= 64, "packed ancestor list: 5-bit joint ids, one 64-bit word");
 constexpr int kMaxLandmarks = 32;  // vertex-landmark keypoints per model
 constexpr int kMaxLmNnz = 8;       // skinning weights per landmark vertex (SMPL has <= 4)
 constexpr int kFrameParams = 76;   // [s, rootAA, rootT, jointAA[1..23]]
@@ -124,6 +126,7 @@ __host__ __device__ inline int fold_slot_gram(int i, int j) { return 2 + 11 * i 
 
 struct PriorArgs {
   int F, nS, beta_stride, has_gmm, n_pairs, n_tiles;   // n_tiles = 0: no prior workgroups
+  int npose;                                           // frame parameters per row: 7 + 3 (n_joints - 1)
   double beta_pose, beta_shape, lambda_t;
   DevGmm g;
   const double* beta;

@@ -503,7 +503,7 @@ __device__ __forceinline__ void frame_part(const DevModel& M, const DevProblem& 
   };
   auto lm_terms = [&](int l, const double (&pdv)[27]) {
     const int k = min(lm_k + 1, nJ - 1);
-    const bool on = l < nL && lm_k < nJ - 1;
+    const bool lm_on = l < nL, on = lm_on && lm_k < nJ - 1;   // (one joint: no blend item, lane 0 still writes the row)
     const double onf = (lm_blend && on) ? 1.0 : 0.0;      // (masked lanes loaded a clamped, valid row)
     double part[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -534,7 +534,7 @@ __device__ __forceinline__ void frame_part(const DevModel& M, const DevProblem& 
 #pragma unroll
       for (int off = 16; off > 0; off >>= 1) part[a] += __shfl_xor(part[a], off, 32);
     }
-    if (on && lm_k == 0) {
+    if (lm_on && lm_k == 0) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) sLm[l * LM_STRIDE + LM_VP + a] = sPart[l * 3 + a] + part[a];
     }

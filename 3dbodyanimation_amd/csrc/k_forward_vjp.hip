@@ -243,14 +243,14 @@ __global__ __launch_bounds__(128) void k_vjp_skin_t(const int* __restrict__ csr_
 struct VjpChainArgs {
   DevModel M;
   int F, use_shape, beta_stride, pose_blend;
-  const double* params;     // [F(+1)][76]
+  const double* params;     // [F(+1)][npose], npose = 7 + 3 (nJ - 1)
   const double* beta;       // may be null (zeros)
   const double* R0;         // [F][9]
   const double* dT;         // [F][24][12] or null
   const float* part;        // [n_chunks][Fp][224] or null
   int n_chunks, Fp;
   const double* H;          // [F][nJ][3] or null
-  double* gx;               // [F][76]
+  double* gx;               // [F][npose]
   double* gbeta;            // [F][nS] (per frame, or the shared sum's inputs); may be null
 };
 
@@ -268,8 +268,8 @@ __global__ __launch_bounds__(64) void k_vjp_chain(VjpChainArgs a) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= a.F) return;
   const DevModel& M = a.M;
-  const int nJ = M.nJ, nS = M.nS;
-  const double* x = a.params + (size_t)f * kFrameParams;
+  const int nJ = M.nJ, nS = M.nS, npose = 7 + 3 * (nJ - 1);
+  const double* x = a.params + (size_t)f * npose;
   const bool shp = a.use_shape && nS > 0;                  // (no beta given: the forward's beta = 0)
   double beta[kMaxShape];
   for (int k = 0; k < kMaxShape; ++k) beta[k] = (shp && a.beta && k < nS) ? a.beta[(size_t)f * a.beta_stride + k] : 0.0;
@@ -387,14 +387,13 @@ __global__ __launch_bounds__(64) void k_vjp_chain(VjpChainArgs a) {
         gb[k] += M.dS[(j * 3) * nS + k] * go[0] + M.dS[(j * 3 + 1) * nS + k] * go[1] + M.dS[(j * 3 + 2) * nS + k] * go[2];
   }
   // ---- out --------------------------------------------------------------------------------------------------------------
-  double* g = a.gx + (size_t)f * kFrameParams;
+  double* g = a.gx + (size_t)f * npose;
   g[0] = gs;
   double gRroot[9];                                        // Rr0 = Rroot R0: gRroot = gRr0 R0^T
   mul33_bt(gRr0, a.R0 + (size_t)f * 9, gRroot);
   rot_grad(x + 1, gRroot, g + 1);
   g[4] = gt[0]; g[5] = gt[1]; g[6] = gt[2];
   for (int j = 1; j < nJ; ++j) rot_grad(x + 7 + 3 * (j - 1), gR[j], g + 7 + 3 * (j - 1));
-  for (int i = 7 + 3 * (nJ - 1); i < kFrameParams; ++i) g[i] = 0.0;
   if (a.gbeta)
     for (int k = 0; k < nS; ++k) a.gbeta[(size_t)f * nS + k] = gb[k];
 }

@@ -23,12 +23,26 @@ constexpr int kPriorTileF = 16;   // frames per prior workgroup (MFMA M)
 constexpr int kPriorNT = 5;       // column tiles of 16 (69 -> 80)
 constexpr int kPriorKS = 18;      // k-steps of 4 (69 -> 72)
 
+// Temporal rows of this tile's pairs: rootT, rootAA, then the joint angles; rows of npose - 1 entries (NPc = 0: A.npose).
+template <int NPc>
+__device__ inline void temporal_rows(const PriorArgs& A, int f0, const double* __restrict__ params, double& pcost) {
+  const int npose = NPc > 0 ? NPc : A.npose, T = npose - 1;
+  for (int i = threadIdx.x; i < kPriorTileF * T; i += 512) {
+    const int f = f0 + i / T, c = i % T;
+    if (f < A.n_pairs) {
+      const int src = (c < 3) ? (4 + c) : (c < 6 ? (1 + (c - 3)) : (7 + (c - 6)));
+      const double v = A.lambda_t * (params[(size_t)f * npose + src] - params[(size_t)(f + 1) * npose + src]);
+      A.r_temporal[(size_t)f * T + c] = v; pcost += 0.5 * v * v;
+    }
+  }
+}
+
 // Written for the 512-thread (8-wave) workgroups of k_frame_resjac: one mixture component per wave (K <= 8).
 __device__ inline void prior_block(const PriorArgs& A, int tile, const double* __restrict__ params, double* sm) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   constexpr int NT = 512;
   const int f0 = tile * kPriorTileF, F = A.F;
-  const int npose = kFrameParams, D = npose - 7;
+  const int npose = kFrameParams, D = npose - 7;   // (the pose prior is built for 24 joints only: bodyfit_problem_create)
   double* sx = sm;                       // [16][72]
   double* sval = sm + kPriorTileF * 72;  // [8][16]
   double pcost = 0.0;                    // 1/2 sum of squares of the rows this thread writes (folded shared-beta reduction)
@@ -144,16 +158,9 @@ __device__ inline void prior_block(const PriorArgs& A, int tile, const double* _
       for (int i = tid; i < A.nS; i += NT) { const double v = A.beta_shape * A.beta[i]; A.r_shape[i] = v; pcost += 0.5 * v * v; }
     }
   }
-  if (A.lambda_t > 0.0 && A.r_temporal) {
-    const int T = 6 + D;
-    for (int i = tid; i < kPriorTileF * T; i += NT) {
-      const int f = f0 + i / T, c = i % T;
-      if (f < A.n_pairs) {
-        const int src = (c < 3) ? (4 + c) : (c < 6 ? (1 + (c - 3)) : (7 + (c - 6)));
-        const double v = A.lambda_t * (params[(size_t)f * npose + src] - params[(size_t)(f + 1) * npose + src]);
-        A.r_temporal[(size_t)f * T + c] = v; pcost += 0.5 * v * v;
-      }
-    }
+  if (A.lambda_t > 0.0 && A.r_temporal) {   // (SMPL's 76-wide rows with a compile-time width, other joint counts at run time)
+    if (A.npose == kFrameParams) temporal_rows<kFrameParams>(A, f0, params, pcost);
+    else temporal_rows<0>(A, f0, params, pcost);
   }
   if (A.plain_cost) {   // this tile's share of 1/2 |r|^2 over the prior / shape / temporal rows, fixed-order block sum
 #pragma unroll

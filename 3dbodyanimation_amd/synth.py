@@ -119,7 +119,7 @@ class SynthModel:
 
     def finalize(self):
         self.J0 = self.j_regressor @ self.v_template
-        self.S = np.einsum("jv,vak->jak", self.j_regressor, self.shapedirs).reshape(3 * self.n_joints, -1)
+        self.S = np.einsum("jv,vak->jak", self.j_regressor, self.shapedirs).reshape(3 * self.n_joints, self.n_shape)
         return self
 
 
@@ -273,7 +273,7 @@ def forward_numpy(model: SynthModel, x: np.ndarray, beta: np.ndarray, R0: np.nda
     vids = np.asarray(vids, dtype=np.int64)
     vp = model.v_template[vids] - Jb[0] + model.shapedirs[vids] @ b
     if pose_blend:
-        feat = np.concatenate([(Rl[j] - np.eye(3)).reshape(-1) for j in range(1, nJ)])
+        feat = np.array([(Rl[j] - np.eye(3)).reshape(-1) for j in range(1, nJ)]).reshape(-1)   # (empty for one joint)
         vp = vp + model.posedirs[vids] @ feat
     out = np.zeros((len(vids), 3))
     Wv = model.weights[vids]

@@ -67,7 +67,12 @@ typedef struct bodyfit_model bodyfit_model;     /* device-resident SMPL model   
 typedef struct bodyfit_gmm bodyfit_gmm;         /* device-resident max-mixture pose prior */
 typedef struct bodyfit_problem bodyfit_problem; /* residual blocks of one solve           */
 
-/* SMPL tensors, host pointers, row-major f64 (the reference keeps Eigen doubles).          */
+/* SMPL tensors, host pointers, row-major f64 (the reference keeps Eigen doubles).          *
+ * Accepted model shapes: any n_verts; 1 <= n_joints <= 24; 0 <= n_shape <= 10; n_pose_feat 0 or 9 (n_joints - 1);    *
+ * a topologically ordered tree at most 13 levels deep below the root (deeper: BODYFIT_ERR_INVALID).  A frame's          *
+ * parameter row is 7 + 3 (n_joints - 1) wide (76 for 24 joints).  Below 24 joints only the frame role is built:          *
+ * keypoint residuals, Jacobian, joints, temporal rows, shape prior and the joints-only VJP; the pose prior               *
+ * (beta_pose > 0), the mesh path (want_mesh, the cloud VJP) and the solvers need 24 joints.                          */
 typedef struct bodyfit_model_desc {
   int n_verts;               /* 6890 */
   int n_joints;              /* 24   */
@@ -78,7 +83,7 @@ typedef struct bodyfit_model_desc {
   const double* posedirs;    /* [n_verts][3][n_pose_feat] or NULL */
   const double* j_regressor; /* [n_joints][n_verts]       */
   const double* weights;     /* [n_verts][n_joints]       */
-  const int* parent;         /* [n_joints], root = -1 (scripts/npz_fixer.py) */
+  const int* parent;         /* [n_joints], root = -1 (scripts/npz_fixer.py); parent[j] < j; depth <= 13 */
   int n_landmarks;           /* vertex-landmark keypoints (0 = none) */
   const int* landmark_vid;   /* [n_landmarks] vertex ids  */
   /* Sparse keypoint regressors over the POSED vertices (0 = none): keypoint id n_joints + n_landmarks + r is
@@ -127,7 +132,7 @@ typedef struct bodyfit_problem_desc {
                              shape block, if present, gets zero columns (MultiFrameBA.h:88)   */
   int beta_per_frame;     /* 0: one shared beta[n_shape]; 1: beta[n_frames][n_shape]          */
   int pose_blend;         /* apply posedirs in vertex landmarks and the mesh                  */
-  double beta_pose;       /* PosePriorAAAnalytic weight; 0 = no prior block                   */
+  double beta_pose;       /* PosePriorAAAnalytic weight; 0 = no prior block (> 0 needs 24 joints) */
   const bodyfit_gmm* gmm; /* NULL = L2 fallback (include/Sim3BA.h:283)                        */
   double beta_shape;      /* ShapePriorL2Analytic weight; 0 = none                            */
   double lambda_temporal; /* Vec3DiffCost weight between frames f, f+1; 0 = none              */
