@@ -198,6 +198,10 @@ def load_library():
     lib.bodyfit_forward_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_forward_vjp.argtypes = [C.c_void_p, _dp, _dp, _fp, _dp, _dp, _dp]
+    lib.bodyfit_residuals_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.bodyfit_residual_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_void_p]
+    lib.bodyfit_residual_vjp.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
     lib.bodyfit_writeback_batch.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _dp]
     lib.bodyfit_evaluate_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_dp), _dp, C.POINTER(_dp)]
     _u8p = C.POINTER(C.c_uint8)
@@ -380,12 +384,17 @@ class Problem:
         self.beta_per_frame = bool(beta_per_frame)
         self.n_param_rows = self.n_frames + (1 if temporal_halo else 0)
         self.n_frame_params = 7 + 3 * (model.n_joints - 1)   # 76 for SMPL's 24 joints
+        self.huber_delta = float(huber_delta)
+        # bumped by every call that sweeps or solves into the problem's buffers: torch_layer.FitObjective reuses the Jacobian of
+        # its forward in its backward only if nothing else ran on the problem in between
+        self.generation = 0
 
     @classmethod
     def from_sequence(cls, model: Model, seq, **kw):
         return cls(model, seq.kp_offset, seq.kp_id, seq.kp_uv, seq.intr, seq.R0, **kw)
 
     def evaluate(self, frame_params, beta=None, want_jacobian=True):
+        self.generation += 1
         L = self.layout
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
         assert x.size == self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
@@ -395,6 +404,7 @@ class Problem:
         return r, J, comp
 
     def evaluate_device(self, d_params_ptr: int, d_beta_ptr: int | None, want_jacobian=True, stream: int | None = None):
+        self.generation += 1
         _check(load_library().bodyfit_evaluate_device(self.h, d_params_ptr, d_beta_ptr, int(want_jacobian), stream))
 
     def reduce_shared_device(self, d_out_ptr: int | None = None, stream: int | None = None):
@@ -424,6 +434,7 @@ class Problem:
         _check(load_library().bodyfit_arm_shared_reduction(self.h, d_out_ptr))
 
     def profile_sweep(self, d_params_ptr, d_beta_ptr, want_jacobian=True, with_reduce=False, iters=50, stream=None):
+        self.generation += 1
         ms = np.zeros(5)
         _check(load_library().bodyfit_profile_sweep(self.h, d_params_ptr, d_beta_ptr, int(want_jacobian),
                                                     int(with_reduce), int(iters), stream, _d(ms)))
@@ -436,6 +447,7 @@ class Problem:
         return v
 
     def forward(self, frame_params, beta=None, want_cloud=True):
+        self.generation += 1
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
         assert x.size >= self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         joints = np.empty((self.n_frames, self.model.n_joints, 3))
@@ -447,6 +459,7 @@ class Problem:
     def forward_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_joints_ptr: int | None, d_cloud_ptr: int | None,
                        cloud_row_floats: int | None = None, stream: int | None = None):
         """bodyfit_forward_device: the two-launch forward into device memory, asynchronous on `stream`."""
+        self.generation += 1
         rf = 3 * self.model.n_verts if cloud_row_floats is None else int(cloud_row_floats)
         _check(load_library().bodyfit_forward_device(self.h, d_params_ptr, d_beta_ptr, d_joints_ptr, d_cloud_ptr, rf, stream))
 
@@ -478,9 +491,42 @@ class Problem:
         _check(load_library().bodyfit_forward_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_cloud_ptr, rf,
                                                          d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr, stream))
 
+    def residuals_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_residuals_ptr: int, d_comp_ptr: int | None = None,
+                         keep_jacobian=False, stream: int | None = None):
+        """bodyfit_residuals_device: the residual vector [total_rows] f64 (and the GMM components [F] int32) into device memory,
+        asynchronous on `stream`; keep_jacobian also leaves the Jacobian for residual_vjp_device(..., reuse_jacobian=True)."""
+        self.generation += 1
+        _check(load_library().bodyfit_residuals_device(self.h, d_params_ptr, d_beta_ptr, d_residuals_ptr, d_comp_ptr,
+                                                       int(keep_jacobian), stream))
+
+    def residual_vjp_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_grad_r_ptr: int, d_grad_params_ptr: int,
+                            d_grad_beta_ptr: int | None, reuse_jacobian=False, stream: int | None = None):
+        """bodyfit_residual_vjp_device: (dr/dx)^T g and (dr/dbeta)^T g of the whole residual vector, asynchronous on `stream`.
+        reuse_jacobian: use the Jacobian of the problem's last sweep (residuals_device with keep_jacobian at this point)."""
+        if not reuse_jacobian:
+            self.generation += 1
+        _check(load_library().bodyfit_residual_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_r_ptr, d_grad_params_ptr,
+                                                          d_grad_beta_ptr, int(bool(reuse_jacobian)), stream))
+
+    def residual_vjp(self, frame_params, beta, grad_r):
+        """(dr/dframe_params)^T g [F(+1), 7 + 3 (nJ - 1)] and (dr/dbeta)^T g ([nS] shared, [F, nS] per frame; None without the
+        shape block) of the whole residual vector r [total_rows] at (frame_params, beta), g = grad_r (bodyfit_residual_vjp)."""
+        self.generation += 1
+        x = _c64(frame_params); b = _c64(beta) if beta is not None else None
+        g = _c64(grad_r)
+        assert x.size == self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
+        assert g.size == self.layout.total_rows, "grad_r must be [total_rows]"
+        gx = np.empty((self.n_param_rows, self.n_frame_params))
+        gb = None
+        if self.n_cols > self.n_frame_params:
+            gb = np.empty((self.n_frames, self.model.n_shape)) if self.beta_per_frame else np.empty(self.model.n_shape)
+        _check(load_library().bodyfit_residual_vjp(self.h, _d(x), _d(b), _d(g), _d(gx), _d(gb)))
+        return gx, gb
+
     def writeback(self, frame_params, beta=None, want_cloud=False):
         """The reference's post-solve write-back for every frame, on the device (bodyfit_writeback_batch):
         R0' = R(rootAA) R0, update() without the Sim3 scale, mean pixel error of the FK keypoints."""
+        self.generation += 1
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
         F = self.n_frames
         r0 = np.empty((F, 3, 3)); joints = np.empty((F, self.model.n_joints, 3)); px = np.empty(F)
@@ -492,6 +538,7 @@ class Problem:
     def solve(self, frame_params, beta=None, constant=None, independent=False, max_iters=100, scale_bounds=(0.3, 3.0),
               verbose=False, solver=0):
         """Ceres-like LM over this problem (bodyfit_solve).  Returns fitted params, beta, [FitSummary]."""
+        self.generation += 1
         x = _c64(frame_params).copy()
         b = _c64(beta).copy() if beta is not None else None
         cst = None
@@ -508,6 +555,7 @@ class Problem:
                       verbose=False):
         """This rank's shard of one window (bodyfit_solve_sharded).  frame_params: the shard's rows (+ the halo row when the
         problem has one).  Returns the shard's fitted rows, beta (the same on every rank) and the FitSummary."""
+        self.generation += 1
         x = _c64(frame_params).copy()
         b = _c64(beta).copy()
         assert x.size == self.n_param_rows * N_FRAME_PARAMS
@@ -523,6 +571,7 @@ class Problem:
                            scale_bounds=(-1e300, 1e300), verbose=False):
         """This rank's shard of one window with the exchanges as RCCL all-gathers on the solve's device buffers and stream
         (bodyfit_solve_sharded_rccl)."""
+        self.generation += 1
         x = _c64(frame_params).copy()
         b = _c64(beta).copy()
         assert x.size == self.n_param_rows * N_FRAME_PARAMS
@@ -541,12 +590,14 @@ class Problem:
     def cache_sweep(self, params, beta=None):
         """One sweep kept in the problem's host cache for evaluate_block (what bodyfit_ceres::SweepCallback does): no caller
         buffers, so only the structurally non-zero Jacobian column blocks cross PCIe."""
+        self.generation += 1
         x = _c64(params)
         b = _c64(beta) if beta is not None else None
         _check(load_library().bodyfit_evaluate_batch(self.h, _d(x), _d(b) if b is not None else None, None, None, None, 1))
 
     def evaluate_block(self, kind: int, index: int, blocks: list[np.ndarray], n_res: int, want=None):
         """ceres::CostFunction::Evaluate on one block.  `want[b]` False -> jacobians[b] = NULL."""
+        self.generation += 1
         blocks = [_c64(b) for b in blocks]
         nb = len(blocks)
         params = (_dp * nb)(*[_d(b) for b in blocks])

@@ -264,6 +264,12 @@ struct bodyfit_problem {
   float* vjp_bbuf = nullptr;
   float* vjp_part = nullptr;
   double* vjp_dT = nullptr;
+  // residual VJP (k_residual_vjp.hip): whether d_J / d_comp hold the dense Jacobian of the last sweep (a Jacobian sweep into the
+  // problem's own buffers sets it; residual-only sweeps, the solves and every other writer of d_r / d_J clear it), the per-frame
+  // beta partials of a shared beta and the GMM prior's transposed factor rows, both allocated on the first residual VJP
+  bool jac_current = false;
+  double* rvjp_gbf = nullptr;
+  double* rvjp_gmm = nullptr;
   Allocs mem;
 };
 
@@ -350,6 +356,7 @@ int sweep(bodyfit_problem* p, const double* d_params, const double* d_beta, int 
           bool skip_priors = false, double* J_base = nullptr) {
   const bodyfit_model* m = p->m;
   DevProblem dp = p->d;
+  p->jac_current = false;
   if (R0_override) dp.R0 = R0_override;
   dp.beta_partials = (want_jac && !frame_flags) ? p->d_frame_partials : nullptr;
   dp.huber = p->desc.huber_delta;
@@ -425,8 +432,16 @@ int sweep(bodyfit_problem* p, const double* d_params, const double* d_beta, int 
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  // the dense Jacobian of every frame and the components of this point are now in the problem's own buffers
+  p->jac_current = want_jac && !r_base && !J_base && !comp_out && !frame_flags && !skip_priors && !R0_override;
   return BODYFIT_OK;
 }
+
+// The solves reuse d_r / d_J / d_comp as their working state: whatever they leave there is no Jacobian a caller may reuse
+struct DropJacobianOnExit {
+  bodyfit_problem* p;
+  ~DropJacobianOnExit() { p->jac_current = false; }
+};
 
 }  // namespace
 
@@ -1316,6 +1331,7 @@ int bodyfit_internal_solve_batched_device(bodyfit_problem* p, double* frame_para
   HIP_TRY(hipSetDevice(m->device));
   std::lock_guard<std::mutex> lock(p->mu);
   p->cache_valid = false;
+  DropJacobianOnExit drop_jacobian{p};
   LmState S{};
   LmProblem P{};
   P.F = F; P.ncols = n; P.kp_offset = p->d.kp_offset;
@@ -1516,6 +1532,7 @@ static int solve_window_device(bodyfit_problem* p, double* frame_params, double*
                                bodyfit_fit_summary* summary, Transport* comm, bool force_sharded) {
   const bodyfit_model* m = p->m;
   const int F = p->d.F, npose = 7 + 3 * (m->nJ - 1), n = p->lay.n_cols, nb = n - npose;
+  DropJacobianOnExit drop_jacobian{p};
   // shard proxy (bodyfit_set_shard_proxy): through a ONE-rank communicator this problem runs as rank proxy_rank of proxy_ranks
   // identical shards — every kernel, buffer and exchange of that geometry, the gathered slots filled with copies of its own
   const bool proxy = comm != nullptr && comm->size == 1 && p->proxy_ranks > 1;
@@ -1976,6 +1993,10 @@ long bodyfit_launch_count(void) { return g_launch_count.load(std::memory_order_r
 
 int bodyfit_internal_fail(int code, const char* msg) { return fail(code, msg ? msg : ""); }
 
+void bodyfit_internal_drop_jacobian(bodyfit_problem* p) {
+  if (p) p->jac_current = false;
+}
+
 int bodyfit_internal_solver_view(bodyfit_problem* p, bodyfit_solver_view* out) {
   if (!p || !out) return BODYFIT_ERR_INVALID;
   out->n_frames = p->d.F; out->n_joints = p->m->nJ; out->n_shape = p->m->nS;
@@ -2096,6 +2117,7 @@ int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, con
   // the two-launch sweep without Jacobian or priors: joints straight into the caller's buffer, the cloud through the problem's
   // padded one
   const PriorArgs none{};
+  p->jac_current = false;   // (its residual rows land in d_r)
   launch_frame_resjac(m->d, p->d, d_frame_params, d_b, p->d_r, nullptr, d_joints ? d_joints : p->d_joints,
                       d_cloud ? p->mc : MeshCoef{}, 0, none, st);
   if (d_cloud) {
@@ -2254,6 +2276,109 @@ int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const do
   p->async_pending = false;   // (NULL stream, waited for below)
   HIP_TRY(hipMemcpy(grad_frame_params, d_gx, npar * sizeof(double), hipMemcpyDeviceToHost));
   if (ngb) HIP_TRY(hipMemcpy(grad_beta, d_gb, ngb * sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  return BODYFIT_OK;
+}
+
+int bodyfit_residuals_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, double* d_residuals,
+                             int* d_gmm_comp, int keep_jacobian, void* stream) {
+  if (!p || !d_frame_params || !d_residuals) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const bool has_beta = p->lay.n_cols > 7 + 3 * (m->nJ - 1);
+  if (has_beta && !d_beta) return fail(BODYFIT_ERR_INVALID, "beta required when the shape block is present");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  p->async_stream = st;
+  p->async_pending = true;
+  // the sweep without the mesh (k_frame_resjac and its prior workgroups): residuals, Jacobian and components are those of the
+  // one-launch sweep
+  if (int rc = sweep(p, d_frame_params, has_beta ? d_beta : nullptr, keep_jacobian ? 1 : 0, false, st)) return rc;
+  if (p->lay.total_rows > 0)
+    HIP_TRY(hipMemcpyAsync(d_residuals, p->d_r, (size_t)p->lay.total_rows * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (d_gmm_comp) HIP_TRY(hipMemcpyAsync(d_gmm_comp, p->d_comp, (size_t)p->d.F * sizeof(int), hipMemcpyDeviceToDevice, st));
+  return BODYFIT_OK;
+}
+
+int bodyfit_residual_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                const double* d_grad_residuals, double* d_grad_frame_params, double* d_grad_beta,
+                                int reuse_jacobian, void* stream) {
+  if (!p || !d_frame_params || !d_grad_residuals || !d_grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const int npose = 7 + 3 * (m->nJ - 1), F = p->d.F, nS = m->nS;
+  const bool has_beta = p->lay.n_cols > npose, per_frame = p->desc.beta_per_frame != 0;
+  if (has_beta && !d_grad_beta) return fail(BODYFIT_ERR_INVALID, "grad_beta is required when n_cols = 76 + n_shape");
+  if (has_beta && !reuse_jacobian && !d_beta) return fail(BODYFIT_ERR_INVALID, "beta required when the shape block is present");
+  if (reuse_jacobian && !p->jac_current)
+    return fail(BODYFIT_ERR_INVALID, "reuse_jacobian: the problem's buffers hold no current Jacobian (none since creation, or "
+                                     "a later sweep or solve overwrote it)");
+  HIP_TRY(hipSetDevice(m->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (has_beta && !per_frame && !p->rvjp_gbf) HIP_TRY(p->mem.alloc(&p->rvjp_gbf, (size_t)F * nS));
+  if (p->has_gmm && p->lay.prior_rows_per_frame > 0 && !p->rvjp_gmm) {
+    // G_k[c][7 + d] = beta_p s L_k[d][c]: row c of the GMM block's transposed Jacobian, in the frame's column layout
+    const int D = npose - 7, K = p->gmm.K;
+    const std::vector<double>& L = p->desc.gmm->prec_cho;
+    const double sc = p->desc.beta_pose * p->gmm.resid_scale;
+    std::vector<double> G((size_t)K * D * npose, 0.0);
+    for (int k = 0; k < K; ++k)
+      for (int c = 0; c < D; ++c)
+        for (int d = 0; d < D; ++d) G[((size_t)k * D + c) * npose + 7 + d] = sc * L[((size_t)k * D + d) * D + c];
+    const double* up = nullptr;
+    HIP_TRY(p->mem.upload(&up, G));
+    p->rvjp_gmm = const_cast<double*>(up);
+  }
+  p->async_stream = st;
+  p->async_pending = true;
+  if (!reuse_jacobian)
+    if (int rc = sweep(p, d_frame_params, has_beta ? d_beta : nullptr, 1, false, st)) return rc;
+  ResVjpArgs a{};
+  a.F = F; a.n_param_rows = p->n_param_rows; a.ncols = p->lay.n_cols; a.npose = npose; a.nS = nS;
+  a.kp_offset = p->d.kp_offset;
+  a.J = p->d_J;
+  a.g = d_grad_residuals;
+  a.row_prior = p->row_prior; a.prior_rows = p->lay.prior_rows_per_frame;
+  a.row_shape = p->row_shape; a.shape_rows = p->lay.shape_rows; a.shape_per_frame = per_frame ? 1 : 0;
+  a.row_temporal = p->row_temporal; a.n_pairs = p->n_pairs;
+  a.beta_pose = p->desc.beta_pose; a.beta_shape = p->desc.beta_shape; a.lambda_t = p->desc.lambda_temporal;
+  a.gmm_rows = p->has_gmm ? p->rvjp_gmm : nullptr;
+  a.comp = p->d_comp;
+  a.gx = d_grad_frame_params;
+  a.gb = has_beta ? (per_frame ? d_grad_beta : p->rvjp_gbf) : nullptr;
+  launch_residual_vjp(a, st);
+  if (has_beta && !per_frame) launch_vjp_beta_sum(p->rvjp_gbf, F, nS, d_grad_beta, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return BODYFIT_OK;
+}
+
+int bodyfit_residual_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const double* grad_residuals,
+                         double* grad_frame_params, double* grad_beta) {
+  if (!p || !frame_params || !grad_residuals || !grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const int npose = 7 + 3 * (m->nJ - 1), F = p->d.F, nS = m->nS;
+  const bool has_beta = p->lay.n_cols > npose;
+  if (has_beta && !grad_beta) return fail(BODYFIT_ERR_INVALID, "grad_beta is required when n_cols = 76 + n_shape");
+  if (has_beta && !beta) return fail(BODYFIT_ERR_INVALID, "beta required when the shape block is present");
+  HIP_TRY(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> lock(p->mu);
+  p->cache_valid = false;
+  if (int ro = order_after_async(p, nullptr)) return ro;
+  const size_t npar = (size_t)p->n_param_rows * npose, nr = (size_t)p->lay.total_rows;
+  const size_t nbeta = has_beta ? (size_t)(p->desc.beta_per_frame ? F * nS : nS) : 0;
+  Allocs tmp;
+  double *d_x = nullptr, *d_b = nullptr, *d_g = nullptr, *d_gx = nullptr, *d_gb = nullptr;
+  HIP_TRY(tmp.alloc(&d_x, npar));
+  HIP_TRY(tmp.alloc(&d_gx, npar));
+  HIP_TRY(tmp.alloc(&d_g, nr));
+  if (nbeta) HIP_TRY(tmp.alloc(&d_b, nbeta));
+  if (nbeta) HIP_TRY(tmp.alloc(&d_gb, nbeta));
+  HIP_TRY(hipMemcpy(d_x, frame_params, npar * sizeof(double), hipMemcpyHostToDevice));
+  if (nr) HIP_TRY(hipMemcpy(d_g, grad_residuals, nr * sizeof(double), hipMemcpyHostToDevice));
+  if (nbeta) HIP_TRY(hipMemcpy(d_b, beta, nbeta * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = bodyfit_residual_vjp_device(p, d_x, d_b, d_g, d_gx, d_gb, 0, nullptr)) return rc;
+  p->async_pending = false;   // (NULL stream, waited for below)
+  HIP_TRY(hipMemcpy(grad_frame_params, d_gx, npar * sizeof(double), hipMemcpyDeviceToHost));
+  if (nbeta) HIP_TRY(hipMemcpy(grad_beta, d_gb, nbeta * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipDeviceSynchronize());
   return BODYFIT_OK;
 }

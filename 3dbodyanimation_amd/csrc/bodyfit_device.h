@@ -372,4 +372,21 @@ void launch_vjp_chain(const DevModel& M, const DevProblem& P, const double* d_pa
                       const float* d_part, const double* d_H, double* d_gx, double* d_gbeta_frames, hipStream_t s);
 void launch_vjp_beta_sum(const double* d_gbeta_frames, int F, int nS, double* d_out, hipStream_t s);
 
+// vector-Jacobian product of the whole residual vector (k_residual_vjp.hip; bodyfit_residual_vjp_device)
+struct ResVjpArgs {
+  int F, n_param_rows, ncols, npose, nS;
+  const int* kp_offset;       // [F + 1] (device copy of the problem's keypoint CSR)
+  const double* J;            // [2K][ncols] reprojection panel of the sweep
+  const double* g;            // [total_rows] upstream gradient
+  int row_prior, prior_rows;  // prior_rows: 0, D (L2) or D + 1 (GMM) per frame
+  int row_shape, shape_rows, shape_per_frame;
+  int row_temporal, n_pairs;
+  double beta_pose, beta_shape, lambda_t;
+  const double* gmm_rows;     // [K][D][npose] beta_p s L_k^T rows at columns 7.. (GMM prior) or NULL (L2)
+  const int* comp;            // [F] mixture component of each frame (GMM)
+  double* gx;                 // [n_param_rows][npose]
+  double* gb;                 // [F][nS]: per-frame beta rows (beta_per_frame) or partials (shared beta), NULL without a shape block
+};
+void launch_residual_vjp(const ResVjpArgs& a, hipStream_t s);
+
 }  // namespace bodyfit

@@ -560,9 +560,23 @@ bool solve_step(const Normal& N, const std::vector<double>& scale, const unsigne
 
 }  // namespace
 
+static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, const unsigned char* param_constant,
+                      int independent_frames, const bodyfit_fit_options* opt_in, bodyfit_fit_summary* summaries,
+                      int n_summaries);
+extern "C" __attribute__((weak)) void bodyfit_internal_drop_jacobian(bodyfit_problem* p);
+
+// every loop below evaluates into the problem's own buffers: after a solve they hold no Jacobian a residual VJP may reuse
 extern "C" int bodyfit_solve(bodyfit_problem* p, double* frame_params, double* beta,
                              const unsigned char* param_constant, int independent_frames,
                              const bodyfit_fit_options* opt_in, bodyfit_fit_summary* summaries, int n_summaries) {
+  const int rc = solve_impl(p, frame_params, beta, param_constant, independent_frames, opt_in, summaries, n_summaries);
+  if (bodyfit_internal_drop_jacobian) bodyfit_internal_drop_jacobian(p);   // (weak: absent from CPU builds of this file)
+  return rc;
+}
+
+static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, const unsigned char* param_constant,
+                      int independent_frames, const bodyfit_fit_options* opt_in, bodyfit_fit_summary* summaries,
+                      int n_summaries) {
   if (!p || !frame_params) return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_solve: null argument");
   bodyfit_solver_view view;
   if (bodyfit_internal_solver_view(p, &view) != BODYFIT_OK) return BODYFIT_ERR_INVALID;

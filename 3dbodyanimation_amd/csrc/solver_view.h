@@ -13,6 +13,8 @@ typedef struct bodyfit_solver_view {
 } bodyfit_solver_view;
 int bodyfit_internal_solver_view(bodyfit_problem* p, bodyfit_solver_view* out);
 int bodyfit_internal_fail(int code, const char* msg);
+/* The problem's buffers no longer hold a Jacobian that bodyfit_residual_vjp_device(..., reuse_jacobian = 1) may use (solves). */
+void bodyfit_internal_drop_jacobian(bodyfit_problem* p);
 int bodyfit_internal_solve_batched_device(bodyfit_problem* p, double* frame_params, double* beta,
                                           const unsigned char* param_constant, const bodyfit_fit_options* opt,
                                           bodyfit_fit_summary* summaries, int n_summaries);   /* sets bodyfit_last_error(), returns code */

@@ -279,6 +279,36 @@ int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params,
 int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* grad_cloud,
                         const double* grad_joints, double* grad_frame_params, double* grad_beta);
 
+/* ---- the fitting objective as a differentiable function of (frame_params, beta) ----------------------------------------
+ * Residual vector into caller memory: the sweep at (frame_params, beta) (without the mesh), then an asynchronous copy of the
+ * problem's residuals [total_rows] (bodyfit_problem_layout row order) to d_residuals and, if d_gmm_comp [F] is not NULL, of the
+ * GMM components.  keep_jacobian = 1 runs the Jacobian sweep, so that a following
+ * bodyfit_residual_vjp_device(..., reuse_jacobian = 1) can skip its own sweep.  d_beta is required with the shape block.
+ * Ordered like bodyfit_evaluate_device (it uses the problem's sweep buffers).                                              */
+int bodyfit_residuals_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, double* d_residuals,
+                             int* d_gmm_comp, int keep_jacobian, void* stream);
+/* Vector-Jacobian product of the WHOLE residual vector, given d_grad_residuals [total_rows] = dL/dr:
+ *   d_grad_frame_params [F(+1)][7 + 3 (nJ - 1)] = (dr/dframe_params)^T g (the halo row of a temporal_halo problem receives the
+ *   last temporal pair's -lambda g and nothing else), d_grad_beta [nS] (shared) or [F][nS] (beta_per_frame) = (dr/dbeta)^T g.
+ * Row kinds: reprojection (the sweep's dense panel), pose prior (L2: beta_p I; GMM: beta_p s L_k^T, s = the mixture's
+ * resid_scale, k = the frame's component at that sweep — the derivative of the residual as the sweep computes it; the
+ * reference's analytic Jacobian of that block, which the solvers and bodyfit_evaluate_block reproduce, omits s; the constant
+ * last row contributes nothing), shape prior (beta_s I), temporal (+-lambda I).
+ * reuse_jacobian = 0: runs the Jacobian sweep at (frame_params, beta) first.  reuse_jacobian = 1: uses the Jacobian and GMM
+ * components of the problem's last sweep, which the caller guarantees was at this point; BODYFIT_ERR_INVALID when the buffers
+ * hold no current dense Jacobian (none since creation, or the last sweep was residual-only, or a solve or another sweep wrote
+ * them since).  d_grad_beta is required when n_cols = 7 + 3 (nJ - 1) + nS, may be NULL otherwise (with use_shape = 0 only the
+ * shape prior reaches it).  BODYFIT_ERR_INVALID also for NULL problem / frame_params / grad_residuals / grad_frame_params.
+ * Asynchronous on `stream`, ordered like bodyfit_evaluate_device.  Deterministic: no atomics, fixed summation orders; a frame's
+ * rows depend on that frame's rows of J and g only (bit-identical whatever F); a shared beta sums per-frame partials in a
+ * fixed order.  The first call on a problem allocates (and, with a GMM prior, uploads) a little state of its own.           */
+int bodyfit_residual_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                const double* d_grad_residuals, double* d_grad_frame_params, double* d_grad_beta,
+                                int reuse_jacobian, void* stream);
+/* Host-pointer form, synchronous, always re-sweeps. */
+int bodyfit_residual_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const double* grad_residuals,
+                         double* grad_frame_params, double* grad_beta);
+
 /* The post-solve write-back of a whole solve on the device: for every frame
  *   r[0] <- R(rootAA) r[0]  (left-multiplied, so it compounds over repeated solves),  p <- rootT,
  *   r[j] <- R(jointAA[j]),  Avatar::update()  (the Sim3 scale is dropped),
