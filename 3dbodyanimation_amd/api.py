@@ -123,6 +123,20 @@ class DeviceViews(C.Structure):
                 ("cloud_frame_stride", C.c_longlong)]
 
 
+class PointSet(C.Structure):   # bodyfit_pointset (include/bodyfit.h): device pointers
+    """f32 xyz rows on the device, per frame: uniform (n_per_frame rows, frame_stride floats between frames) or ragged (d_offset:
+    a device int32 CSR [F + 1] over one packed [N][3] array)."""
+    _fields_ = [("d_xyz", C.c_void_p), ("d_offset", C.c_void_p), ("n_per_frame", C.c_int), ("frame_stride", C.c_longlong)]
+
+    @classmethod
+    def uniform(cls, d_xyz_ptr: int, n_per_frame: int, frame_stride: int | None = None) -> "PointSet":
+        return cls(d_xyz_ptr, None, int(n_per_frame), 3 * int(n_per_frame) if frame_stride is None else int(frame_stride))
+
+    @classmethod
+    def ragged(cls, d_xyz_ptr: int, d_offset_ptr: int) -> "PointSet":
+        return cls(d_xyz_ptr, d_offset_ptr, 0, 0)
+
+
 _lib = None
 
 
@@ -202,6 +216,13 @@ def load_library():
     lib.bodyfit_residual_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p]
     lib.bodyfit_residual_vjp.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+    lib.bodyfit_closest_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.bodyfit_closest_destroy.argtypes = [C.c_void_p]
+    lib.bodyfit_closest_destroy.restype = None
+    lib.bodyfit_closest_points_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.POINTER(PointSet), C.c_int, C.c_longlong,
+                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.bodyfit_closest_points_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.POINTER(PointSet), C.c_int, C.c_longlong,
+                                                      C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_writeback_batch.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _dp]
     lib.bodyfit_evaluate_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_dp), _dp, C.POINTER(_dp)]
     _u8p = C.POINTER(C.c_uint8)
@@ -612,6 +633,47 @@ class Problem:
     def close(self):
         if getattr(self, "h", None):
             load_library().bodyfit_problem_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ClosestPoints:
+    """Closest points between two per-frame point sets on the device, and the gradient of the squared distances with the
+    correspondence held fixed (bodyfit_closest_*, csrc/k_closest.hip).  The handle owns the workspace of both calls; calls on
+    one handle must be ordered (one stream, or events)."""
+
+    def __init__(self, device: int = 0):
+        h = C.c_void_p()
+        _check(load_library().bodyfit_closest_create(int(device), C.byref(h)))
+        self.h = h
+        self.device = device
+
+    def points_device(self, query: PointSet, ref: PointSet, n_frames: int, n_query_total: int, n_ref_total: int,
+                      d_dist2_ptr: int, d_index_ptr: int, stream: int | None = None, prepare_vjp: bool = False):
+        """bodyfit_closest_points_device: dist2 [N] f32 and frame-local index [N] int32 (-1: none) of every query row,
+        asynchronous on `stream`.  n_query_total / n_ref_total: row counts of ragged sets (ignored for uniform ones).
+        prepare_vjp: also group the queries by reference row for a points_vjp_device call with this index (kept in the handle)."""
+        _check(load_library().bodyfit_closest_points_device(self.h, C.byref(query), C.byref(ref), int(n_frames),
+                                                            int(n_query_total), int(n_ref_total), d_dist2_ptr, d_index_ptr,
+                                                            int(bool(prepare_vjp)), stream))
+
+    def points_vjp_device(self, query: PointSet, ref: PointSet, n_frames: int, n_query_total: int, n_ref_total: int,
+                          d_index_ptr: int, d_grad_dist2_ptr: int, d_grad_query_ptr: int | None, d_grad_ref_ptr: int | None,
+                          stream: int | None = None):
+        """bodyfit_closest_points_vjp_device: dL/dquery and dL/dref (each in the layout of its set; either may be None) given
+        dL/ddist2 [N] and the index of points_device, asynchronous on `stream`."""
+        _check(load_library().bodyfit_closest_points_vjp_device(self.h, C.byref(query), C.byref(ref), int(n_frames),
+                                                                int(n_query_total), int(n_ref_total), d_index_ptr,
+                                                                d_grad_dist2_ptr, d_grad_query_ptr, d_grad_ref_ptr, stream))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().bodyfit_closest_destroy(self.h)
             self.h = None
 
     def __del__(self):

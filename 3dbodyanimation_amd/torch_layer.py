@@ -14,6 +14,13 @@ that problem's device buffers, so interleaving them on several streams at once n
     (obj.cost(r) + my_term).backward()      # backward: bodyfit_residual_vjp_device (k_residual_vjp.hip)
 
 obj.cost(r) is the Ceres cost of the problem (HuberLoss on the keypoint blocks, squares elsewhere), written in torch.
+
+    dist2, index = closest_points(points, verts, query_offset=offset)   # every scan point against its frame's vertices
+    term = PointCloudTerm(points, offset)                               # sum of (truncated) squared distances
+    (obj.cost(obj(x, beta)) + w * term(layer(x, beta)[0])).backward()   # keypoints + priors + scan
+
+closest_points is bodyfit_closest_points_device (k_closest.hip: brute force from LDS, no [F, N, V] intermediate); its backward is
+bodyfit_closest_points_vjp_device, with the correspondence held fixed, deterministic like the other gradients here.
 """
 from __future__ import annotations
 
@@ -202,3 +209,141 @@ class FitObjective(torch.nn.Module):
         kp = r[:K2].view(-1, 2)
         rest = r[K2:]
         return 0.5 * huber_rho(self.problem.huber_delta, (kp * kp).sum(dim=1)).sum() + 0.5 * (rest * rest).sum()
+
+
+# ---- 3-D point-cloud term -----------------------------------------------------------------------------------------------
+_closest_handles: dict[int, object] = {}
+
+
+def _closest_handle(device_index: int):
+    h = _closest_handles.get(device_index)
+    if h is None:
+        h = _closest_handles[device_index] = api.ClosestPoints(device_index)
+    return h
+
+
+def _point_set(name: str, t, offset):
+    """(tensor to keep alive, api.PointSet, frames, rows) of a uniform [F, n, 3] or ragged [N, 3] + offset [F + 1] point tensor."""
+    if not isinstance(t, torch.Tensor) or (offset is not None and not isinstance(offset, torch.Tensor)):
+        raise TypeError(f"{name} and its offset must be torch tensors")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be on the GPU")
+    if offset is None:
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError(f"{name} must be [F, n, 3] (or [N, 3] with an offset), got {tuple(t.shape)}")
+        F, n = t.shape[0], t.shape[1]
+        # a view with a frame stride of its own (the library's padded cloud) is used in place when its [n, 3] blocks are dense
+        dense = t.stride(2) == 1 and t.stride(1) == 3 and (F == 1 or t.stride(0) >= 3 * n)
+        if not dense or F * n == 0:
+            t = t.contiguous()
+        stride = t.stride(0) if F > 1 and F * n > 0 else 3 * n
+        return t, api.PointSet.uniform(t.data_ptr(), n, stride), F, F * n
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} with an offset must be [N, 3], got {tuple(t.shape)}")
+    if offset.dtype != torch.int32 or offset.ndim != 1 or offset.shape[0] < 1:
+        raise TypeError(f"{name}'s offset must be an int32 tensor [F + 1]")
+    if offset.device != t.device:
+        raise ValueError(f"{name} and its offset must be on the same GPU")
+    t = t.contiguous()
+    offset = offset.contiguous()
+    ps = api.PointSet.ragged(t.data_ptr(), offset.data_ptr())
+    ps._keep = offset
+    return t, ps, offset.shape[0] - 1, t.shape[0]
+
+
+def _grad_like(t: torch.Tensor, ps) -> torch.Tensor:
+    """an uninitialised gradient in the layout of point set ps (whose tensor is t)"""
+    if ps.d_offset is None and t.ndim == 3 and t.shape[0] > 1 and t.stride(0) != 3 * t.shape[1]:
+        F, n = t.shape[0], t.shape[1]
+        return torch.empty((F, t.stride(0)), dtype=torch.float32, device=t.device)[:, :3 * n].view(F, n, 3)
+    return torch.empty(t.shape, dtype=torch.float32, device=t.device)
+
+
+class _ClosestPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, query, ref, query_offset, ref_offset):
+        q, qs, F, nq = _point_set("query", query, query_offset)
+        r, rs, Fr, nr = _point_set("ref", ref, ref_offset)
+        if F != Fr:
+            raise ValueError(f"query has {F} frames, ref has {Fr}")
+        if r.device != q.device:
+            raise ValueError("query and ref must be on the same GPU")
+        handle = _closest_handle(q.device.index)
+        dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+        index = torch.empty(nq, dtype=torch.int32, device=q.device)
+        if nq > 0:
+            # (the reference set's gradient needs the queries grouped by reference row: built with the search, once)
+            handle.points_device(qs, rs, F, nq, nr, dist2.data_ptr(), index.data_ptr(), _stream(),
+                                 prepare_vjp=ctx.needs_input_grad[1])
+        ctx.sets = (qs, rs, F, nq, nr, handle)
+        ctx.save_for_backward(q, r, index)
+        ctx.mark_non_differentiable(index)
+        return dist2, index
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_dist2, _g_index):
+        q, r, index = ctx.saved_tensors
+        qs, rs, F, nq, nr, handle = ctx.sets
+        want_q, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gq = _grad_like(q, qs) if want_q else None
+        gr = _grad_like(r, rs) if want_r else None
+        if g_dist2 is None or nq == 0:
+            for g in (gq, gr):
+                if g is not None:
+                    g.zero_()
+        else:
+            g = g_dist2.to(torch.float32).contiguous()
+            handle.points_vjp_device(qs, rs, F, nq, nr, index.data_ptr(), g.data_ptr(),
+                                     gq.data_ptr() if gq is not None else None,
+                                     gr.data_ptr() if gr is not None else None, _stream())
+        return gq, gr, None, None
+
+
+def closest_points(query: torch.Tensor, ref: torch.Tensor, query_offset: torch.Tensor | None = None,
+                   ref_offset: torch.Tensor | None = None):
+    """For every query point the closest reference point of the same frame: (dist2 [N] f32, index [N] int32, frame-local, -1
+    and +inf where the frame has no reference point), packed in frame order.
+
+    A point set is f32 on the GPU, either uniform, [F, n, 3] (a view whose frames are farther apart than 3 n floats, such as
+    the library's padded cloud, is used without a copy), or ragged, [N, 3] with an int32 offset [F + 1] on the same GPU
+    (offset[0] = 0, offset[F] = N, non-decreasing: not checked, that would synchronise).
+    dist2 is differentiable with respect to both point tensors with the correspondence held fixed (the ICP / Chamfer gradient);
+    index carries no gradient.  Runs on torch.cuda.current_stream() without a host synchronisation (bodyfit_closest_points_device
+    and bodyfit_closest_points_vjp_device, k_closest.hip).  Calls on one GPU share a workspace: interleaving them on several
+    streams at once needs the caller's own ordering."""
+    return _ClosestPoints.apply(query, ref, query_offset, ref_offset)
+
+
+class PointCloudTerm(torch.nn.Module):
+    """The 3-D data term of a sequence: sum over the target points of rho(squared distance to the closest vertex of the frame),
+    plus, when bidirectional, the same from every vertex to the closest target point of its frame.
+
+    points: [N, 3] f32 on the GPU with offset, int32 [F + 1] (a depth map, scan or marker set per frame; frames may be empty),
+    or [F, n, 3] with offset None.  trunc = tau: rho(s) = min(s, tau^2), so points farther than tau from the body (background)
+    stop pulling; None: rho(s) = s.  term(verts), verts [F, V, 3] f32 (SMPLLayer's first output), returns the f64 cost."""
+
+    def __init__(self, points: torch.Tensor, offset: torch.Tensor | None = None, bidirectional: bool = False,
+                 trunc: float | None = None):
+        super().__init__()
+        _point_set("points", points, offset)   # the checks
+        if trunc is not None and not trunc > 0.0:
+            raise ValueError("trunc must be positive")
+        self.register_buffer("points", points.detach())
+        self.register_buffer("offset", offset.detach() if offset is not None else None)
+        self.bidirectional = bool(bidirectional)
+        self.trunc = None if trunc is None else float(trunc)
+
+    def _rho(self, dist2, index):
+        s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))   # (a frame without a counterpart: +inf, costs nothing)
+        if self.trunc is not None:
+            s = torch.clamp(s, max=self.trunc * self.trunc)
+        return s.double().sum()
+
+    def forward(self, verts: torch.Tensor) -> torch.Tensor:
+        cost = self._rho(*closest_points(self.points, verts, query_offset=self.offset))
+        if self.bidirectional:
+            cost = cost + self._rho(*closest_points(verts, self.points, ref_offset=self.offset))
+        return cost

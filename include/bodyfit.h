@@ -309,6 +309,56 @@ int bodyfit_residual_vjp_device(bodyfit_problem* p, const double* d_frame_params
 int bodyfit_residual_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const double* grad_residuals,
                          double* grad_frame_params, double* grad_beta);
 
+/* ---- closest points between two per-frame point sets (the 3-D data term: scan / depth map / markers against the mesh) -----
+ * A point set is f32 xyz rows on the device, organised per frame either uniformly (n_per_frame rows, frame_stride floats
+ * between frames: bodyfit_device_views.cloud with its cloud_frame_stride, or a dense [F][n][3] array with stride 3 n) or
+ * ragged (d_offset: a device int32 CSR [n_frames + 1] over one packed [N][3] array, the convention of kp_offset; frames may be
+ * empty; d_offset[0] must be 0 and d_offset[n_frames] the set's row count: nothing checks it, since that would read the
+ * offsets back).  The query set and the reference set may each be of either kind.                                          */
+typedef struct bodyfit_pointset {
+  const float* d_xyz;
+  const int32_t* d_offset;   /* [n_frames + 1] CSR (ragged), or NULL: uniform                         */
+  int n_per_frame;           /* uniform only                                                          */
+  long long frame_stride;    /* uniform only, in floats, >= 3 n_per_frame                             */
+} bodyfit_pointset;
+typedef struct bodyfit_closest bodyfit_closest;   /* per-device workspace (partial minima, the groupings of the last searches) */
+int bodyfit_closest_create(int device, bodyfit_closest** out);
+void bodyfit_closest_destroy(bodyfit_closest* h);
+/* For every query point p of frame f, over the reference points c_v of the same frame:
+ *   d_index = argmin_v |p - c_v|^2, frame-local (-1 if the frame has no reference point, or every distance is NaN),
+ *   d_dist2 = |p - c_index|^2 (+inf if none),
+ * both packed in frame order: row d_offset[f] + i of a ragged query set, f n_per_frame + i of a uniform one.  The distance is
+ * evaluated in f32 in the difference form (px - cx)^2 + (py - cy)^2 + (pz - cz)^2, so with D(v) the exact squared distance of
+ * the two f32 points D(index) <= (1 + 2^-19) min_v D(v) and |dist2 - D(index)| <= 2^-20 D(index).  Among equal computed
+ * distances the lowest index wins.  Deterministic, and a frame's outputs depend on that frame only (bit-identical whatever
+ * n_frames).  n_query_total / n_ref_total: the row count of a ragged set (so that no call reads d_offset back to the host);
+ * ignored for a uniform set.  prepare_vjp = 1 also groups the queries by the reference row they chose (integer work on the
+ * index alone, about the cost of the gradient itself) and keeps that in the handle, so that
+ * bodyfit_closest_points_vjp_device with this call's d_index is one launch; the handle keeps the groupings of its last four
+ * such calls.  Asynchronous on `stream` (a hipStream_t as void*; NULL: the default stream); a call that has to
+ * grow the handle's workspace synchronises the device once.  Calls on one handle share that workspace: order them (one stream,
+ * or events).  n_frames == 0 or no query rows: a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / sets / outputs,
+ * negative counts, frame_stride < 3 n_per_frame, 2^31 rows or more in a set.                                              */
+int bodyfit_closest_points_device(bodyfit_closest* h, const bodyfit_pointset* query, const bodyfit_pointset* ref, int n_frames,
+                                  long long n_query_total, long long n_ref_total, float* d_dist2, int32_t* d_index,
+                                  int prepare_vjp, void* stream);
+/* Reverse-mode gradient with the correspondence held fixed (the ICP / Chamfer gradient): given d_index (as above; -1 or an
+ * index outside the frame: the query contributes nothing and gets a zero gradient) and d_grad_dist2 = dL/ddist2 (packed like
+ * d_dist2),
+ *   d_grad_query[i] = -2 g_i (c_index_i - p_i),        d_grad_ref[v] = sum over {i : index_i = v} of 2 g_i (c_v - p_i),
+ * each in the layout of its point set (same d_offset / n_per_frame / frame_stride; every row of a frame is written, zeros
+ * where no query maps; the padding between the frames of a uniform set is left untouched).  Either output may be NULL.  f32
+ * throughout.  Deterministic: no float atomics; a reference row sums its queries in a fixed order that depends on that
+ * frame's data only (ascending query row; a row that more than 64 queries chose: 64 interleaved ascending partial sums, then a
+ * fixed tree), so a frame's gradients are bit-identical whatever n_frames and from run to run.  The grouping that dL/dref
+ * needs is taken from the handle when d_index is the output pointer of one of its last four prepare_vjp searches over the same
+ * sets and counts — the caller guarantees that the array has not been written since, and orders the two calls (one stream, or
+ * events); any other d_index is grouped inside this call, at several launches more, with the same result bit for bit.
+ * Asynchronous and ordered like bodyfit_closest_points_device.                                                             */
+int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset* query, const bodyfit_pointset* ref,
+                                      int n_frames, long long n_query_total, long long n_ref_total, const int32_t* d_index,
+                                      const float* d_grad_dist2, float* d_grad_query, float* d_grad_ref, void* stream);
+
 /* The post-solve write-back of a whole solve on the device: for every frame
  *   r[0] <- R(rootAA) r[0]  (left-multiplied, so it compounds over repeated solves),  p <- rootT,
  *   r[j] <- R(jointAA[j]),  Avatar::update()  (the Sim3 scale is dropped),
