@@ -343,7 +343,7 @@ void launch_reduce_shared_ex(int K, int ncols, int npose, int nS, int total_rows
                              const double* d_J, double huber_delta, int shape_row0, int shape_rows,
                              double beta_shape, double* d_partials, double* d_out66, hipStream_t s);
 int reduce_partials_doubles();
-// the non-zero column blocks of every reprojection block's Jacobian, contiguous (bodyfit_api.hip: packed cache of the host path)
+// the non-zero column blocks of every reprojection block's Jacobian, contiguous (api_problem.hip: packed cache of the host path)
 void launch_pack_jacobian(int K, int ncols, int n_joint_blocks, const double* d_J, const unsigned* d_mask, const unsigned* d_off,
                           double* d_out, const double* d_r, int nr, double* r_out, const int* d_comp, int ncomp, int* comp_out,
                           hipStream_t s);

@@ -40,6 +40,7 @@
 
 #include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
+#include "host_state.h"
 #include "solver_view.h"
 
 namespace bodyfit {
@@ -415,13 +416,6 @@ __global__ __launch_bounds__(256) void k_cp_vjp(const VjpArgs a) {
   else vjp_ref_rows(a, (long long)(blockIdx.x - a.qblocks) * 256 + threadIdx.x);
 }
 
-#define CP_TRY(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return bodyfit_internal_fail(BODYFIT_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
 int invalid(const char* fn, const char* what) {
   return bodyfit_internal_fail(BODYFIT_ERR_INVALID, (std::string(fn) + ": " + what).c_str());
 }
@@ -484,9 +478,9 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // `*p` holds at least `bytes` (growing frees the old block, which waits for the device: calls on a handle are ordered)
 int reserve(char** p, size_t* have, size_t bytes) {
   if (bytes <= *have) return 0;
-  if (*p) { CP_TRY(hipFree(*p)); *p = nullptr; *have = 0; }
+  if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; *have = 0; }
   bytes += bytes / 4;
-  CP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), bytes));
   *have = bytes;
   return 0;
 }
@@ -521,8 +515,8 @@ int build_grouping(bodyfit_closest* h, const bodyfit_pointset* query, const body
   a.rowid = reinterpret_cast<int*>(h->ws + a_nq);
   a.perm = reinterpret_cast<int*>(h->ws + 2 * a_nq);
   a.cursor = reinterpret_cast<int*>(h->ws + 3 * a_nq);
-  CP_TRY(hipMemsetAsync(a.cnt, 0, (size_t)nr * 4, st));
-  CP_TRY(hipMemsetAsync(a.cursor, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(a.cnt, 0, (size_t)nr * 4, st));
+  HIP_TRY(hipMemsetAsync(a.cursor, 0, 4, st));
   const unsigned qblocks = (unsigned)((nq + 255) / 256), rblocks = (unsigned)((nr + 255) / 256);
   if (qblocks) {
     BODYFIT_LAUNCH(k_cp_group_count, dim3(qblocks), dim3(256), 0, st, a);
@@ -531,7 +525,7 @@ int build_grouping(bodyfit_closest* h, const bodyfit_pointset* query, const body
     BODYFIT_LAUNCH(k_cp_group_rank, dim3(qblocks), dim3(256), 0, st, a);
     BODYFIT_LAUNCH(k_cp_group_heavy, dim3(rblocks), dim3(256), 0, st, a);
   }
-  CP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   g->index = d_index; g->q_offset = query->d_offset; g->r_offset = ref->d_offset;
   g->q_n = query->n_per_frame; g->r_n = ref->n_per_frame;
   g->F = F; g->nq = nq; g->nr = nr;
@@ -550,9 +544,9 @@ int bodyfit_closest_create(int device, bodyfit_closest** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return bodyfit_internal_fail(BODYFIT_ERR_HIP, "bodyfit_closest_create: no such HIP device (there is no CPU path)");
-  CP_TRY(hipSetDevice(device));
+  HIP_TRY(hipSetDevice(device));
   int n_cu = 0;
-  CP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
   bodyfit_closest* h = new bodyfit_closest;
   h->device = device;
   h->n_cu = n_cu > 0 ? n_cu : 256;
@@ -580,7 +574,7 @@ int bodyfit_closest_points_device(bodyfit_closest* h, const bodyfit_pointset* qu
   if (!d_dist2 || !d_index) return invalid(fn, "d_dist2 / d_index is NULL");
   if (!h) return invalid(fn, "null handle");
   if (n_frames == 0 || n_query_total == 0) return BODYFIT_OK;
-  CP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   // d_index is about to change: a grouping kept for this pointer is void
   for (Grouping& g : h->groupings)
@@ -611,7 +605,7 @@ int bodyfit_closest_points_device(bodyfit_closest* h, const bodyfit_pointset* qu
   BODYFIT_LAUNCH(k_closest, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kWaves), 0, st, a);
   if (a.n_split > 1)
     BODYFIT_LAUNCH(k_closest_reduce, dim3((unsigned)((n_query_total + 255) / 256)), dim3(256), 0, st, a);
-  CP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   if (group) {   // (behind the reduction on the stream: the scratch may lie over the partial minima)
     Grouping* g = nullptr;
     if (int rc = build_grouping(h, query, ref, n_frames, n_query_total, n_ref_total, d_index, true, st, &g)) return rc;
@@ -631,7 +625,7 @@ int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset
   if (!h) return invalid(fn, "null handle");
   if (n_frames == 0 || (!d_grad_query && !d_grad_ref)) return BODYFIT_OK;
   if (n_query_total == 0 && (!d_grad_ref || n_ref_total == 0)) return BODYFIT_OK;
-  CP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   VjpArgs a{};
   a.q = device_set(query); a.r = device_set(ref);
@@ -652,7 +646,7 @@ int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset
     a.cnt = g->cnt; a.start = g->start; a.sorted = g->sorted;
   }
   if (a.qblocks + rblocks) BODYFIT_LAUNCH(k_cp_vjp, dim3(a.qblocks + rblocks), dim3(256), 0, st, a);
-  CP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }
 

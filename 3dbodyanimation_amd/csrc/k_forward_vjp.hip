@@ -1,6 +1,6 @@
 // k_forward_vjp.hip — reverse-mode gradient (vector-Jacobian product) of the SMPL forward that bodyfit_forward computes:
 // given G = dL/dcloud ([F][V][3] f32) and H = dL/djoints ([F][24][3] f64), either optional, dL/dframe_params ([F][76] f64)
-// and dL/dbeta.  Host side: bodyfit_forward_vjp_device (bodyfit_api.hip).
+// and dL/dbeta.  Host side: bodyfit_forward_vjp_device (api_vjp.hip).
 //
 // For frame f (frame_part_inl.h, mesh_part_inl.h):
 //   T_j     = s Rr0 [A_j | P_j - A_j Jc_j] + [0 | t],  Rr0 = R(rootAA) R0,  A_j = A_par R_j,  P_j = A_par o_j + P_par

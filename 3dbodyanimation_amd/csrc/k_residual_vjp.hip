@@ -1,6 +1,6 @@
 // k_residual_vjp.hip — vector-Jacobian product of the WHOLE residual vector of a problem (bodyfit_residual_vjp_device):
 // given g = dL/dr over the rows of bodyfit_problem_layout, dL/dframe_params = (dr/dx)^T g and dL/dbeta = (dr/dbeta)^T g.
-// Host side: bodyfit_api.hip.
+// Host side: api_vjp.hip.
 //
 // Row kinds and their Jacobians (as the sweep writes the rows: k_sweep.hip, priors_inl.h):
 //   reprojection  the dense [2K][n_cols] panel of the sweep (d_J); frame f owns rows 2 kp_offset[f] .. 2 kp_offset[f+1] - 1

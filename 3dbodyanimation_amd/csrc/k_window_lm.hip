@@ -6,7 +6,7 @@
 // on the host; here it is solved on the device, parallel in the frames, by BLOCK CYCLIC REDUCTION with the border carried
 // as 11 right-hand sides [B | rhs]:
 //   level l: every second remaining frame j (neighbours a < j < b) is eliminated (the larger independent set when the count
-//   is odd: bodyfit_api.hip build_cr_schedule):
+//   is odd: api_solve.hip build_cr_schedule):
 //       D_j = L L^T,  P = L^-1 U_a^T,  Q = L^-1 U_j,  Y = L^-1 R_j                         (k_cr_factor, two workgroups per j)
 //       D_a -= P^T P,  D_b -= Q^T Q,  U_a := -P^T Q,  R_a -= P^T Y,  R_b -= Q^T Y          (k_cr_update, f64 MFMA)
 //   after ceil(log2 F) levels one frame is left: x = D^-1 R; then down again: x_j = L^-T (Y - P x_a - Q x_b)  (k_cr_back)
@@ -1294,7 +1294,7 @@ __global__ __launch_bounds__(256) void k_win_decide(WinProblem P, WinBuf W, doub
     poison = fmax(poison, o[6]);
   }
   if (poison != 0.0) {
-    // A rank could not produce its part of this iteration (a failed launch / HIP call: bodyfit_api.hip puts a 1 in slot 6 of its
+    // A rank could not produce its part of this iteration (a failed launch / HIP call: api_solve.hip puts a 1 in slot 6 of its
     // scalars and keeps taking part in the exchanges).  Every rank reads the same gathered scalars, so every rank ends the solve
     // HERE, in the same iteration: nothing moves, the host loops find the solve inactive at their next status read and return.
     if (tid == 0) {

@@ -30,6 +30,7 @@
 
 #include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
+#include "host_state.h"
 #include "solver_view.h"
 
 #pragma clang fp contract(off)
@@ -735,13 +736,6 @@ size_t tile_lds_bytes(int nF) {
   return 256 * 4 + kTileList * 4 + 256 * 4 + kTile * 4 + (size_t)nWords * 8 + 64;
 }
 
-#define OV_TRY(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return bodyfit_internal_fail(BODYFIT_ERR_HIP, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-  } while (0)
-
 }  // namespace
 
 struct bodyfit_overlay {
@@ -792,7 +786,7 @@ int bodyfit_overlay_create(const bodyfit_overlay_desc* desc, bodyfit_overlay** o
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || desc->device < 0 || desc->device >= ndev)
     return bodyfit_internal_fail(BODYFIT_ERR_HIP, "bodyfit_overlay_create: no such HIP device (there is no CPU path)");
-  OV_TRY(hipSetDevice(desc->device));
+  HIP_TRY(hipSetDevice(desc->device));
   auto* ov = new bodyfit_overlay;
   ov->device = desc->device; ov->nV = desc->n_vertices; ov->nF = desc->n_faces; ov->W = desc->width; ov->H = desc->height;
   ov->maxFrames = desc->max_frames;
@@ -844,7 +838,7 @@ int bodyfit_overlay_render_device(bodyfit_overlay* ov, const void* d_cloud, int 
   if ((n_frames > 1 && cloud_frame_stride_elems < (size_t)ov->nV * 3) || row_stride < (size_t)ov->W * 3 ||
       (n_frames > 1 && frame_stride < row_stride * (size_t)ov->H))
     return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_render: strides smaller than the data");
-  OV_TRY(hipSetDevice(ov->device));
+  HIP_TRY(hipSetDevice(ov->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int F = n_frames, nF = ov->nF;
   const size_t nT = (size_t)F * ov->tilesX * ov->tilesY;
@@ -852,7 +846,7 @@ int bodyfit_overlay_render_device(bodyfit_overlay* ov, const void* d_cloud, int 
   const int nBlocks = (int)((nT + 1 + kScanBlock - 1) / kScanBlock);
   ov->lastFrames = F;
   ov->timed = false;
-  OV_TRY(hipEventRecord(ov->ev[0], st));
+  HIP_TRY(hipEventRecord(ov->ev[0], st));
   {
     dim3 grid((nF + 255) / 256, F);
     if (cloud_is_f64)
@@ -864,22 +858,22 @@ int bodyfit_overlay_render_device(bodyfit_overlay* ov, const void* d_cloud, int 
                          cloud_frame_stride_elems, ov->d_faces, nF, ov->nV, fx, fy, cx, cy, backface_cull, ov->d_tmp,
                          ov->d_key);
   }
-  OV_TRY(hipEventRecord(ov->ev[1], st));
-  OV_TRY(hipMemsetAsync(ov->d_alive, 0, sizeof(int) * F, st));
+  HIP_TRY(hipEventRecord(ov->ev[1], st));
+  HIP_TRY(hipMemsetAsync(ov->d_alive, 0, sizeof(int) * F, st));
   BODYFIT_LAUNCH(k_ov_sort_chunks, dim3(ov->nChunks, F), dim3(kSortThreads), kChunk * 12, st, ov->d_key, nF,
                      ov->nChunks, ov->d_skey, ov->d_sidx);
   BODYFIT_LAUNCH(k_ov_rank, dim3((ov->nChunks * kChunk + 255) / 256, F), dim3(256), 0, st, ov->d_skey, ov->d_sidx, nF,
                      ov->nChunks, ov->d_tmp, ov->d_sorted, ov->d_alive);
-  OV_TRY(hipEventRecord(ov->ev[2], st));
+  HIP_TRY(hipEventRecord(ov->ev[2], st));
   if (!fill && !wireframe) {   // the reference draws nothing (RenderSMPLMesh.h:97,106)
-    OV_TRY(hipEventRecord(ov->ev[3], st));
-    OV_TRY(hipEventRecord(ov->ev[4], st));
-    OV_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ov->ev[3], st));
+    HIP_TRY(hipEventRecord(ov->ev[4], st));
+    HIP_TRY(hipGetLastError());
     ov->timed = true;
     return BODYFIT_OK;
   }
-  OV_TRY(hipMemsetAsync(ov->d_count, 0, sizeof(unsigned) * (nT + 1), st));
-  OV_TRY(hipMemsetAsync(ov->d_totals, 0, sizeof(unsigned) * 4, st));
+  HIP_TRY(hipMemsetAsync(ov->d_count, 0, sizeof(unsigned) * (nT + 1), st));
+  HIP_TRY(hipMemsetAsync(ov->d_totals, 0, sizeof(unsigned) * 4, st));
   BODYFIT_LAUNCH(k_ov_bin<false>, dim3((nF + 255) / 256, F), dim3(256), 0, st, ov->d_sorted, nF, ov->W, ov->H,
                      ov->tilesX, ov->tilesY, ov->d_count, ov->d_offset, ov->d_entries);
   BODYFIT_LAUNCH(k_ov_scan1, dim3(nBlocks), dim3(256), 0, st, ov->d_count, nT + 1, ov->d_blockSum);
@@ -887,15 +881,15 @@ int bodyfit_overlay_render_device(bodyfit_overlay* ov, const void* d_cloud, int 
   BODYFIT_LAUNCH(k_ov_scan3, dim3(nBlocks), dim3(256), 0, st, ov->d_count, nT + 1, ov->d_blockSum, ov->d_offset,
                      ov->d_active, ov->d_totals);
   unsigned totals[2] = {0, 0};
-  OV_TRY(hipMemcpyAsync(totals, ov->d_totals, sizeof(totals), hipMemcpyDeviceToHost, st));
-  OV_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(totals, ov->d_totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (totals[0] > ov->entriesCap) {
-    if (ov->d_entries) OV_TRY(hipFree(ov->d_entries));
+    if (ov->d_entries) HIP_TRY(hipFree(ov->d_entries));
     ov->d_entries = nullptr;
     ov->entriesCap = 0;
     const size_t want = (size_t)totals[0] + totals[0] / 4 + 1024;
     void* q = nullptr;
-    OV_TRY(hipMalloc(&q, want * sizeof(unsigned)));
+    HIP_TRY(hipMalloc(&q, want * sizeof(unsigned)));
     ov->d_entries = static_cast<unsigned*>(q);
     ov->entriesCap = want;
   }
@@ -904,15 +898,15 @@ int bodyfit_overlay_render_device(bodyfit_overlay* ov, const void* d_cloud, int 
     BODYFIT_LAUNCH(k_ov_bin<true>, dim3((nF + 255) / 256, F), dim3(256), 0, st, ov->d_sorted, nF, ov->W, ov->H,
                        ov->tilesX, ov->tilesY, ov->d_count, ov->d_offset, ov->d_entries);
   }
-  OV_TRY(hipEventRecord(ov->ev[3], st));
+  HIP_TRY(hipEventRecord(ov->ev[3], st));
   if (totals[1]) {
     const int grid = (int)std::min<unsigned>(totals[1], 256u * 64u);
     BODYFIT_LAUNCH(k_ov_tiles, dim3(grid), dim3(kTileThreads), tile_lds_bytes(nF), st, ov->d_tris, nF, ov->W, ov->H,
                        ov->tilesX, ov->tilesY, ov->d_offset, ov->d_entries, ov->d_active, ov->d_totals, d_images,
                        row_stride, frame_stride, (fill ? 1 : 0) | (wireframe ? 2 : 0));
   }
-  OV_TRY(hipEventRecord(ov->ev[4], st));
-  OV_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ov->ev[4], st));
+  HIP_TRY(hipGetLastError());
   ov->timed = true;
   return BODYFIT_OK;
 }
@@ -925,32 +919,32 @@ int bodyfit_overlay_render(bodyfit_overlay* ov, const void* cloud, int cloud_is_
     return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_render: n_frames exceeds max_frames");
   if (row_stride < (size_t)ov->W * 3 || (n_frames > 1 && frame_stride < row_stride * (size_t)ov->H))
     return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_render: strides smaller than the data");
-  OV_TRY(hipSetDevice(ov->device));
+  HIP_TRY(hipSetDevice(ov->device));
   const size_t esz = cloud_is_f64 ? 8 : 4;
   const size_t cbytes = ((size_t)(n_frames - 1) * cloud_frame_stride_elems + (size_t)ov->nV * 3) * esz;
   const size_t ibytes = (size_t)(n_frames - 1) * frame_stride + row_stride * (size_t)ov->H;
   if (cbytes > ov->cloudCap) {
-    if (ov->d_cloud) OV_TRY(hipFree(ov->d_cloud));
+    if (ov->d_cloud) HIP_TRY(hipFree(ov->d_cloud));
     ov->d_cloud = nullptr; ov->cloudCap = 0;
-    OV_TRY(hipMalloc(&ov->d_cloud, cbytes));
+    HIP_TRY(hipMalloc(&ov->d_cloud, cbytes));
     ov->cloudCap = cbytes;
   }
   if (ibytes > ov->imagesCap) {
-    if (ov->d_images) OV_TRY(hipFree(ov->d_images));
+    if (ov->d_images) HIP_TRY(hipFree(ov->d_images));
     ov->d_images = nullptr; ov->imagesCap = 0;
     void* q = nullptr;
-    OV_TRY(hipMalloc(&q, ibytes));
+    HIP_TRY(hipMalloc(&q, ibytes));
     ov->d_images = static_cast<unsigned char*>(q);
     ov->imagesCap = ibytes;
   }
-  OV_TRY(hipMemcpy(ov->d_cloud, cloud, cbytes, hipMemcpyHostToDevice));
-  OV_TRY(hipMemcpy(ov->d_images, images, ibytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ov->d_cloud, cloud, cbytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ov->d_images, images, ibytes, hipMemcpyHostToDevice));
   const int rc = bodyfit_overlay_render_device(ov, ov->d_cloud, cloud_is_f64, cloud_frame_stride_elems, n_frames,
                                                ov->d_images, row_stride, frame_stride, fx, fy, cx, cy, fill,
                                                backface_cull, wireframe, nullptr);
   if (rc) return rc;
-  OV_TRY(hipDeviceSynchronize());
-  OV_TRY(hipMemcpy(images, ov->d_images, ibytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(images, ov->d_images, ibytes, hipMemcpyDeviceToHost));
   return BODYFIT_OK;
 }
 
@@ -959,12 +953,12 @@ int bodyfit_overlay_drawlist(bodyfit_overlay* ov, int frame, int* n_items, int32
   if (!ov || !n_items) return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_drawlist: null argument");
   if (frame < 0 || frame >= ov->lastFrames)
     return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_drawlist: frame was not part of the latest render");
-  OV_TRY(hipSetDevice(ov->device));
-  OV_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipSetDevice(ov->device));
+  HIP_TRY(hipDeviceSynchronize());
   int n = 0;
-  OV_TRY(hipMemcpy(&n, ov->d_alive + frame, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&n, ov->d_alive + frame, sizeof(int), hipMemcpyDeviceToHost));
   std::vector<OvFace> h((size_t)std::max(n, 1));
-  if (n) OV_TRY(hipMemcpy(h.data(), ov->d_sorted + (size_t)frame * ov->nF, sizeof(OvFace) * n, hipMemcpyDeviceToHost));
+  if (n) HIP_TRY(hipMemcpy(h.data(), ov->d_sorted + (size_t)frame * ov->nF, sizeof(OvFace) * n, hipMemcpyDeviceToHost));
   for (int k = 0; k < n; ++k) {
     if (face) face[k] = h[k].face;
     if (gray) gray[k] = h[k].gray;
@@ -978,9 +972,9 @@ int bodyfit_overlay_drawlist(bodyfit_overlay* ov, int frame, int* n_items, int32
 int bodyfit_overlay_last_timing(bodyfit_overlay* ov, float ms[4]) {
   if (!ov || !ms) return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_last_timing: null argument");
   if (!ov->timed) return bodyfit_internal_fail(BODYFIT_ERR_INVALID, "bodyfit_overlay_last_timing: nothing rendered yet");
-  OV_TRY(hipSetDevice(ov->device));
-  OV_TRY(hipEventSynchronize(ov->ev[4]));
-  for (int i = 0; i < 4; ++i) OV_TRY(hipEventElapsedTime(&ms[i], ov->ev[i], ov->ev[i + 1]));
+  HIP_TRY(hipSetDevice(ov->device));
+  HIP_TRY(hipEventSynchronize(ov->ev[4]));
+  for (int i = 0; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ov->ev[i], ov->ev[i + 1]));
   return BODYFIT_OK;
 }
 

@@ -494,7 +494,7 @@ def test_packed_cache_serves_every_block_of_the_dense_panel(api, synth, model, g
 
 
 def test_a_problem_built_from_pooled_blocks_equals_one_built_from_fresh_memory(api, synth, model, gpu_model, oracle_mod, omodel):
-    """Device blocks of a destroyed problem are kept for the next problem of the same shape (BlockPool, bodyfit_api.hip): the
+    """Device blocks of a destroyed problem are kept for the next problem of the same shape (BlockPool, csrc/host_state.h): the
     staged drivers create and destroy two problems per stage.  Stale contents are then the NORMAL case for every buffer the
     creation does not clear (Jacobian, partials, cloud, write-back).  Problem A (one sequence, one set of prior weights) is
     evaluated, solved and destroyed; problem B — same sizes, other keypoints, other weights — takes A's blocks, and must agree bit

@@ -9,8 +9,8 @@ HIPCC=/opt/rocm/bin/hipcc
 BASE="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=14"   # (the Makefile's HIPFLAGS)
 mkdir -p _obj_var/$name
 if [[ $name == st_* ]]; then
-  for f in bodyfit_api k_sweep k_reduce k_lm_batched k_window_lm overlay; do
-    $HIPCC $BASE -DBODYFIT_STAMPS $flags -c $f.hip -o _obj_var/$name/$f.o &
+  for f in *.hip; do
+    $HIPCC $BASE -DBODYFIT_STAMPS $flags -c $f -o _obj_var/$name/${f%.hip}.o &
   done
   wait
   $HIPCC -O3 -mavx2 -mfma -std=c++17 -fPIC -c host_solver.cpp -o _obj_var/$name/host_solver.o
