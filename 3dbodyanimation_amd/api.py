@@ -572,37 +572,36 @@ class Problem:
                                             int(independent), C.byref(opt), sums, n_sum))
         return x, b, list(sums)
 
+    def _solve_shard(self, call, frame_params, beta, constant, max_iters, scale_bounds, verbose):
+        """Marshalling of the two sharded solves: call(x, beta, constant, options, summary) is the ABI function with its
+        communicator bound."""
+        self.generation += 1
+        x = _c64(frame_params).copy()
+        b = _c64(beta).copy()
+        npf = self.n_frame_params
+        assert x.size == self.n_param_rows * npf
+        cst = np.ascontiguousarray(constant, dtype=np.uint8) if constant is not None else None
+        summ = FitSummary()
+        opt = FitOptions(int(max_iters), float(scale_bounds[0]), float(scale_bounds[1]), int(verbose), 3)
+        _check(call(_d(x), _d(b), cst.ctypes.data_as(C.POINTER(C.c_ubyte)) if cst is not None else None, C.byref(opt),
+                    C.byref(summ)))
+        return x.reshape(-1)[:self.n_frames * npf].reshape(self.n_frames, npf).copy(), b, summ
+
     def solve_sharded(self, frame_params, beta, comm: "Comm", constant=None, max_iters=100, scale_bounds=(-1e300, 1e300),
                       verbose=False):
         """This rank's shard of one window (bodyfit_solve_sharded).  frame_params: the shard's rows (+ the halo row when the
         problem has one).  Returns the shard's fitted rows, beta (the same on every rank) and the FitSummary."""
-        self.generation += 1
-        x = _c64(frame_params).copy()
-        b = _c64(beta).copy()
-        assert x.size == self.n_param_rows * N_FRAME_PARAMS
-        cst = np.ascontiguousarray(constant, dtype=np.uint8) if constant is not None else None
-        summ = FitSummary()
-        opt = FitOptions(int(max_iters), float(scale_bounds[0]), float(scale_bounds[1]), int(verbose), 3)
-        _check(load_library().bodyfit_solve_sharded(self.h, _d(x), _d(b),
-                                                    cst.ctypes.data_as(C.POINTER(C.c_ubyte)) if cst is not None else None,
-                                                    C.byref(comm), C.byref(opt), C.byref(summ)))
-        return x.reshape(-1)[:self.n_frames * N_FRAME_PARAMS].reshape(self.n_frames, N_FRAME_PARAMS).copy(), b, summ
+        lib = load_library()
+        return self._solve_shard(lambda x, b, c, o, s: lib.bodyfit_solve_sharded(self.h, x, b, c, C.byref(comm), o, s),
+                                 frame_params, beta, constant, max_iters, scale_bounds, verbose)
 
     def solve_sharded_rccl(self, frame_params, beta, comm: "Rccl", constant=None, max_iters=100,
                            scale_bounds=(-1e300, 1e300), verbose=False):
         """This rank's shard of one window with the exchanges as RCCL all-gathers on the solve's device buffers and stream
         (bodyfit_solve_sharded_rccl)."""
-        self.generation += 1
-        x = _c64(frame_params).copy()
-        b = _c64(beta).copy()
-        assert x.size == self.n_param_rows * N_FRAME_PARAMS
-        cst = np.ascontiguousarray(constant, dtype=np.uint8) if constant is not None else None
-        summ = FitSummary()
-        opt = FitOptions(max_iters, scale_bounds[0], scale_bounds[1], int(verbose), 3)
-        _check(load_library().bodyfit_solve_sharded_rccl(self.h, _d(x), _d(b),
-                                                         cst.ctypes.data_as(C.POINTER(C.c_ubyte)) if cst is not None else None,
-                                                         comm.h, C.byref(opt), C.byref(summ)))
-        return x.reshape(-1)[:self.n_frames * N_FRAME_PARAMS].reshape(self.n_frames, N_FRAME_PARAMS).copy(), b, summ
+        lib = load_library()
+        return self._solve_shard(lambda x, b, c, o, s: lib.bodyfit_solve_sharded_rccl(self.h, x, b, c, comm.h, o, s),
+                                 frame_params, beta, constant, max_iters, scale_bounds, verbose)
 
     def last_exchange_count(self) -> int:
         """all-gathers issued by the last sharded solve of this problem"""

@@ -166,11 +166,6 @@ struct FusedSync {
 constexpr unsigned long long kRoleTimeoutDefault = 5000000;   // 50 ms: give up, set the error word, the host falls back
 constexpr int kRoleMaxFrames = 16384;
 
-// 8-byte write-through store (sc1): the payload form of a hand-off to a workgroup on another XCD inside the launch
-__device__ __forceinline__ void store_f64_through(double* p, double v) {
-  asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
-
 // Tail of a one-launch Jacobian sweep of a shared-shape problem (bodyfit_arm_shared_reduction): every frame / prior workgroup
 // takes a ticket behind its partial ([258] doubles, k_reduce.hip's layout); the LAST one sums the partials in k_reduce_stage2's
 // order and packs [cost | g_beta (10) | upper H_bb (55)] into out66, while the mesh workgroups are still running: the sharded

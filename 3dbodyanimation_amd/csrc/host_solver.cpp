@@ -29,7 +29,10 @@
 #include <vector>
 
 #include "../../include/bodyfit.h"
+#include "lm_rules.h"
 #include "solver_view.h"
+
+using namespace bodyfit;   // lm_rules.h: the trust-region rule shared with the device solvers
 
 namespace {
 
@@ -114,7 +117,7 @@ void parallel_groups(size_t n, Fn&& fn) {
 
 struct Group {  // frames [f0, f1) sharing one LM state (and one beta block when present)
   int f0 = 0, f1 = 0;
-  double radius = 1e4, decrease_factor = 2.0;
+  double radius = kLmInitialRadius, decrease_factor = kLmInitialDecrease;
   double cost = 0.0;
   bool active = true;
   int termination = 1;  // 0 convergence, 1 no convergence (iterations), 2 failure
@@ -704,13 +707,13 @@ static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, co
           gmax = std::max(gmax, std::fabs(gi2));
         }
       for (int i = 0; i < nb; ++i) gmax = std::max(gmax, std::fabs(N.g[nf * NP + i]));
-      if (gmax <= 1e-10) { g.active = false; g.termination = 0; g.why = "gradient tolerance"; return; }
+      if (lm_gradient_tolerance(gmax)) { g.active = false; g.termination = 0; g.why = "gradient tolerance"; return; }
       const double ts0 = timing ? now() : 0.0;
       const bool step_ok = solve_step(N, g.scale, param_constant, g.radius, steps[gi], &model_change[gi]);
       if (timing && groups.size() == 1) t_solve += now() - ts0;
       if (!step_ok) {
-        g.radius /= g.decrease_factor; g.decrease_factor *= 2.0; ++g.n_bad; ++g.iterations;
-        if (g.radius < 1e-32) { g.active = false; g.termination = 2; g.why = "trust region collapsed"; }
+        lm_reject(g.radius, g.decrease_factor); ++g.n_bad; ++g.iterations;
+        if (lm_radius_collapsed(g.radius)) { g.active = false; g.termination = 2; g.why = "trust region collapsed"; }
         return;
       }
       std::vector<double>& d = steps[gi];
@@ -750,7 +753,7 @@ static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, co
       for (int lf = 0; lf < nf; ++lf)
         for (int i = 0; i < NP; ++i) xnorm += x[(size_t)(g.f0 + lf) * NP + i] * x[(size_t)(g.f0 + lf) * NP + i];
       if (nb) { const double* b0 = beta_of(g, xb); for (int i = 0; i < nb; ++i) xnorm += b0[i] * b0[i]; }
-      if (std::sqrt(dn) <= 1e-8 * (std::sqrt(xnorm) + 1e-8)) {
+      if (lm_parameter_tolerance(std::sqrt(dn), std::sqrt(xnorm))) {
         g.active = false; g.termination = 0; g.why = "parameter tolerance";
         for (int lf = 0; lf < nf; ++lf)
           for (int i = 0; i < NP; ++i) xn[(size_t)(g.f0 + lf) * NP + i] = x[(size_t)(g.f0 + lf) * NP + i];
@@ -777,22 +780,21 @@ static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, co
       const double change = g.cost - new_cost;
       const double rho = change / model_change[gi];
       const int nf = g.f1 - g.f0;
-      if (std::isfinite(new_cost) && model_change[gi] > 0.0 && rho > 1e-3) {
+      if (lm_step_accepted(new_cost, model_change[gi], rho)) {
         for (int lf = 0; lf < nf; ++lf)
           std::memcpy(&x[(size_t)(g.f0 + lf) * NP], &xn[(size_t)(g.f0 + lf) * NP], NP * sizeof(double));
         if (nb) std::memcpy(beta_of(g, xb), beta_of(g, xbn), nb * sizeof(double));
         const double old_cost = g.cost;
         g.cost = new_cost;
-        const double t = 2.0 * rho - 1.0;
-        g.radius = std::min(1e16, g.radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-        g.decrease_factor = 2.0;
+        g.radius = lm_radius_after_accept(g.radius, rho);
+        g.decrease_factor = kLmInitialDecrease;
         ++g.n_ok;
         normal_valid[gi] = 0;
         any_accept = true;
-        if (std::fabs(change) < 1e-6 * old_cost) { g.active = false; g.termination = 0; g.why = "function tolerance"; }
+        if (lm_function_tolerance(change, old_cost)) { g.active = false; g.termination = 0; g.why = "function tolerance"; }
       } else {
-        g.radius /= g.decrease_factor; g.decrease_factor *= 2.0; ++g.n_bad;
-        if (g.radius < 1e-32) { g.active = false; g.termination = 2; g.why = "trust region collapsed"; }
+        lm_reject(g.radius, g.decrease_factor); ++g.n_bad;
+        if (lm_radius_collapsed(g.radius)) { g.active = false; g.termination = 2; g.why = "trust region collapsed"; }
       }
       if (opt.verbose && groups.size() == 1)
         std::printf("[bodyfit] it %3d cost %.6e change %.3e rho %.3f radius %.3e\n", g.iterations, g.cost, change, rho, g.radius);

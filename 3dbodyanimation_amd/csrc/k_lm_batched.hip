@@ -15,6 +15,7 @@
 // {sweep, step, residual sweep, accept} per iteration and polls the active-frame counter now and then.
 #include "bodyfit_device.h"
 #include "dense_inl.h"
+#include "lm_rules.h"
 
 namespace bodyfit {
 #ifdef BODYFIT_STAMPS
@@ -48,56 +49,41 @@ static_assert(kRowsMax * kJLd + 69 * 69 <= kMRows * kMLd, "Jhat and the GMM prec
 #define LACC(i, dt)
 #endif
 
-__device__ inline double huber_rho(double delta, double s, double* rho1) {
-  const double b = delta * delta;
-  if (delta > 0.0 && s > b) {
-    const double rt = sqrt(s);
-    *rho1 = delta / rt;
-    return 2.0 * delta * rt - b;
-  }
-  *rho1 = 1.0;
-  return s;
-}
-
-__device__ inline double block_sum(double v, double* red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// cost of one frame from a residual vector: 1/2 sum rho(|r_kp|^2) + 1/2 |prior rows|^2 + 1/2 |shape rows|^2
-// (256 threads: k_lm_init / k_lm_accept; the 512-thread form is frame_cost8 below)
+// cost of one frame from a residual vector: 1/2 sum rho(|r_kp|^2) + 1/2 |prior rows|^2 + 1/2 |shape rows|^2.
+// The first 256 threads (four waves) carry the terms and the sum is the tree over those four waves' slots, whatever the
+// workgroup of NT threads: the 256 threads of k_lm_init / k_lm_accept and the 512 of k_lm_step get the same bits, and with
+// them every decision of the trust region (red[]: one slot per wave of the workgroup)
+template <int NT>
 __device__ double frame_cost(const LmProblem& P, int f, const double* __restrict__ r, double* red, int tid) {
   double acc = 0.0;
-  for (int k = P.kp_offset[f] + tid; k < P.kp_offset[f + 1]; k += 256) {
-    const double r0 = r[2 * (size_t)k], r1 = r[2 * (size_t)k + 1];
-    double r1d;
-    acc += 0.5 * huber_rho(P.huber, r0 * r0 + r1 * r1, &r1d);
-  }
-  for (int i = tid; i < P.prior_rows; i += 256) {
-    const double v = r[P.row_prior + (size_t)f * P.prior_rows + i];
-    acc += 0.5 * v * v;
-  }
-  if (P.shape_rows_per_frame > 0)
-    for (int i = tid; i < P.shape_rows_per_frame; i += 256) {
-      const double v = r[P.row_shape + (size_t)f * P.shape_rows_per_frame + i];
+  if (NT == 256 || tid < 256) {
+    for (int k = P.kp_offset[f] + tid; k < P.kp_offset[f + 1]; k += 256) {
+      const double r0 = r[2 * (size_t)k], r1 = r[2 * (size_t)k + 1];
+      double r1d;
+      acc += 0.5 * huber_rho(P.huber, r0 * r0 + r1 * r1, &r1d);
+    }
+    for (int i = tid; i < P.prior_rows; i += 256) {
+      const double v = r[P.row_prior + (size_t)f * P.prior_rows + i];
       acc += 0.5 * v * v;
     }
-  return block_sum(acc, red, tid);
+    if (P.shape_rows_per_frame > 0)
+      for (int i = tid; i < P.shape_rows_per_frame; i += 256) {
+        const double v = r[P.row_shape + (size_t)f * P.shape_rows_per_frame + i];
+        acc += 0.5 * v * v;
+      }
+  }
+  return block_sum4(acc, red, tid);
 }
 
 __global__ __launch_bounds__(256) void k_lm_init(LmProblem P, LmState S, const double* __restrict__ r) {
   __shared__ double red[4];
   const int f = blockIdx.x, tid = threadIdx.x;
-  const double c = frame_cost(P, f, r, red, tid);
+  const double c = frame_cost<256>(P, f, r, red, tid);
   if (tid == 0) {
     S.cost[f] = c;
     S.initial_cost[f] = c;
-    S.radius[f] = 1e4;
-    S.dec[f] = 2.0;
+    S.radius[f] = kLmInitialRadius;
+    S.dec[f] = kLmInitialDecrease;
     int fl = kLmActive;
     if (!(c == c) || c > 1e300) fl = (2 << kLmTermShift);   // non-finite initial cost: failure
     S.flags[f] = fl;
@@ -106,24 +92,7 @@ __global__ __launch_bounds__(256) void k_lm_init(LmProblem P, LmState S, const d
   }
 }
 
-// f64 value of lane `src` (wave-uniform lane id): two v_readlane_b32
-__device__ __forceinline__ double readlane_f64(double v, int src) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 constexpr int kStepThreads = 512, kStepWaves = 8;
-__device__ inline double block_sum8(double v, double* red, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-}
-
 // k_lm_step runs 512 threads = two waves per SIMD: its serial parts (diagonal blocks, back substitution) belong to wave 0,
 // every other part is spread over all eight waves so that LDS and L2 latency of one wave is covered by its neighbour.
 // Judge the candidate of frame f (cost at the candidate `new_cost` known to every thread): step quality, accept / reject,
@@ -145,7 +114,9 @@ __device__ __forceinline__ bool judge_candidate(const LmProblem& P, const LmStat
   const double cost = T.cost, model = T.model;
   const double change = cost - new_cost;
   const double rho = change / model;
-  const bool accept = (new_cost == new_cost) && new_cost < 1e300 && model > 0.0 && rho > 1e-3;
+  const bool accept = lm_step_accepted(new_cost, model, rho);
+  double rad_bad = T.radius, dec_bad = T.dec;
+  lm_reject(rad_bad, dec_bad);
   int fl = flags & ~kLmHasCand;
   if (accept) {
     if (tid < npose) S.x[(size_t)f * npose + tid] = S.x_new[(size_t)f * npose + tid];
@@ -166,54 +137,25 @@ __device__ __forceinline__ bool judge_candidate(const LmProblem& P, const LmStat
         for (int i = tid - 256; i < nr; i += 256) r_cur[2 * (size_t)k0 + i] = r_new[2 * (size_t)k0 + i];
       }
     }
-    if (fabs(change) < 1e-6 * cost) fl &= ~(kLmActive | kLmTermMask);   // function tolerance
+    if (lm_function_tolerance(change, cost)) fl &= ~(kLmActive | kLmTermMask);   // function tolerance
   } else {
-    if (T.radius / T.dec < 1e-32) fl = (fl & ~(kLmActive | kLmTermMask)) | (2 << kLmTermShift);
+    if (lm_radius_collapsed(rad_bad)) fl = (fl & ~(kLmActive | kLmTermMask)) | (2 << kLmTermShift);
   }
   if (tid == 0) {
     // (straight-line: a branch that picks between S.n_ok and S.n_bad becomes a pointer table in scratch memory)
     const int it0 = S.iters[f], ok0 = S.n_ok[f], bad0 = S.n_bad[f];
-    const double t = 2.0 * rho - 1.0;
-    const double rad_ok = fmin(1e16, T.radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
+    const double rad_ok = lm_radius_after_accept(T.radius, rho);
     S.iters[f] = it0 + 1;
     S.n_ok[f] = ok0 + (accept ? 1 : 0);
     S.n_bad[f] = bad0 + (accept ? 0 : 1);
     S.cost[f] = accept ? new_cost : T.cost;
-    S.radius[f] = accept ? rad_ok : T.radius / T.dec;
-    S.dec[f] = accept ? 2.0 : T.dec * 2.0;
+    S.radius[f] = accept ? rad_ok : rad_bad;
+    S.dec[f] = accept ? kLmInitialDecrease : dec_bad;
     if ((flags & kLmActive) && !(fl & kLmActive)) atomicSub(S.active_count, 1);
     S.flags[f] = fl;
   }
   *flags_io = fl;
   return accept;
-}
-
-// 512-thread form of frame_cost: the first four waves carry exactly frame_cost's terms and the sum is formed in the same
-// order, so the cost (and with it every decision of the trust region) is bit-identical in both forms of the iteration
-__device__ double frame_cost8(const LmProblem& P, int f, const double* __restrict__ r, double* red, int tid) {
-  double acc = 0.0;
-  if (tid < 256) {
-    for (int k = P.kp_offset[f] + tid; k < P.kp_offset[f + 1]; k += 256) {
-      const double r0 = r[2 * (size_t)k], r1 = r[2 * (size_t)k + 1];
-      double r1d;
-      acc += 0.5 * huber_rho(P.huber, r0 * r0 + r1 * r1, &r1d);
-    }
-    for (int i = tid; i < P.prior_rows; i += 256) {
-      const double v = r[P.row_prior + (size_t)f * P.prior_rows + i];
-      acc += 0.5 * v * v;
-    }
-    if (P.shape_rows_per_frame > 0)
-      for (int i = tid; i < P.shape_rows_per_frame; i += 256) {
-        const double v = r[P.row_shape + (size_t)f * P.shape_rows_per_frame + i];
-        acc += 0.5 * v * v;
-      }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = acc;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // Speculative iteration (cand.r != nullptr): the sweep before this launch evaluated residuals AND Jacobian at the
@@ -243,7 +185,7 @@ __global__ __launch_bounds__(kStepThreads) void k_lm_step(LmProblem P, LmState S
   bool use_cand = false;
   if (cand.r && (flags & kLmHasCand)) {
     const TrustState T = load_trust(S, f);
-    const double new_cost = frame_cost8(P, f, cand.r, red, tid);
+    const double new_cost = frame_cost<kStepThreads>(P, f, cand.r, red, tid);
     use_cand = judge_candidate(P, S, f, tid, T, new_cost, cand.r, r_cur, cand.comp, comp_cur, true, &flags);
     __syncthreads();   // x, beta, radius of the new point are read by other threads below (same CU: L1 is shared)
   }
@@ -475,7 +417,7 @@ __global__ __launch_bounds__(kStepThreads) void k_lm_step(LmProblem P, LmState S
   __syncthreads();
   gm = fmax(red[0], red[1]);        // (n <= 86: waves 0 and 1 hold every entry)
   LSTAMP(12);
-  if (gm <= 1e-10) {
+  if (lm_gradient_tolerance(gm)) {
     if (tid == 0) {
       S.flags[f] = (flags & ~(kLmActive | kLmHasCand | kLmTermMask));   // termination 0: convergence
       atomicSub(S.active_count, 1);
@@ -632,14 +574,14 @@ __global__ __launch_bounds__(kStepThreads) void k_lm_step(LmProblem P, LmState S
   }
   if (red[8] == 0.0) {
     if (tid == 0) {
-      const double dec = S.dec[f];
-      const double rad = radius / dec;
+      double rad = radius, dec = S.dec[f];
+      lm_reject(rad, dec);
       S.radius[f] = rad;
-      S.dec[f] = dec * 2.0;
+      S.dec[f] = dec;
       S.n_bad[f] += 1;
       S.iters[f] += 1;
       int fl = flags & ~kLmHasCand;
-      if (rad < 1e-32) { fl = (fl & ~(kLmActive | kLmTermMask)) | (2 << kLmTermShift); atomicSub(S.active_count, 1); }
+      if (lm_radius_collapsed(rad)) { fl = (fl & ~(kLmActive | kLmTermMask)) | (2 << kLmTermShift); atomicSub(S.active_count, 1); }
       S.flags[f] = fl;
     }
     no_candidate();
@@ -754,7 +696,7 @@ __global__ __launch_bounds__(kStepThreads) void k_lm_step(LmProblem P, LmState S
   const double model = red[0] + red[1];
   const double dnorm = sqrt(red[2] + red[3]);
   const double xnorm = sqrt(red[4] + red[5]);
-  if (dnorm <= 1e-8 * (xnorm + 1e-8)) {      // Ceres parameter_tolerance
+  if (lm_parameter_tolerance(dnorm, xnorm)) {
     if (tid == 0) {
       S.flags[f] = (flags & ~(kLmActive | kLmHasCand | kLmTermMask));
       atomicSub(S.active_count, 1);
@@ -875,7 +817,7 @@ __global__ __launch_bounds__(256) void k_lm_accept(LmProblem P, LmState S, const
   int flags = S.flags[f];
   if (!(flags & kLmHasCand)) return;
   const TrustState T = load_trust(S, f);
-  const double new_cost = frame_cost(P, f, r_new, red, tid);
+  const double new_cost = frame_cost<256>(P, f, r_new, red, tid);
   judge_candidate(P, S, f, tid, T, new_cost, r_new, r_cur, comp_new, comp_cur, false, &flags);
 }
 

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "bodyfit_device.h"
+#include "device_util_inl.h"
 
 namespace bodyfit {
 namespace {
@@ -21,12 +22,6 @@ typedef __attribute__((ext_vector_type(4))) double d4;
 constexpr int kRedWavesMax = 4096;  // stage-1 wavefronts (one per workgroup), sized by the launch: 16 MFMA steps each
 constexpr int kRedSteps = 16;       // 4-row MFMA steps per stage-1 wave: all their loads are in flight together
 constexpr int kPartial = 256 + 2;   // 16x16 Gram tile + [huber cost, plain cost] per stage-1 wave
-
-__device__ inline double wave_sum64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Stage 1.  The reprojection rows, robustified by sqrt(rho'), form Jhat = [sqrt(rho') J_beta | sqrt(rho') r]
 // ([2K x 11]).  Its Gram matrix Jhat^T Jhat holds H_bb (10x10), g_beta (column 10) in one symmetric product,

@@ -21,67 +21,21 @@
 // (BlockRegs): written as load-store loops these kernels spent a third of their time in dependent L2 round trips.
 // Blocks are padded to 80 x 80 (identity on the padding), right-hand sides to 16 rows, all stored row-major; "t" buffers
 // hold transposes (Pt[i][k] = P[k][i]) so that every product is  C[i][i'] = sum_k X[i][k] Y[i'][k]  with k contiguous.
-#include "bodyfit_device.h"
+// This unit: the cost functions and the kernels around the linear solve.  The cyclic reduction itself is k_window_cr.hip, the
+// exchange steps of sharded solves k_window_shard.hip; window_lm_inl.h holds what the three share.
 #include "dense_inl.h"
+#include "window_lm_inl.h"
 
 namespace bodyfit {
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double d4;
-constexpr int NP = kFrameParams;     // 76
-constexpr int NBETA = kMaxShape;     // 10
-constexpr int WB = kWinBlock;        // 80
-constexpr int WR = kWinRhs;          // 16
-constexpr int LD = WB + 1;           // LDS leading dimension
 constexpr int kHLd = kNormalLd, kHRows = kNormalRows;   // k_frame_normal panels: 87 x 88, n = 86
-
-__device__ inline double huber_rho_w(double delta, double s) {
-  const double b = delta * delta;
-  if (delta > 0.0 && s > b) return 2.0 * delta * sqrt(s) - b;
-  return s;
-}
-__device__ inline double block_sum_n(double v, double* red, int tid, int nwaves) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nwaves; ++w) s += red[w];
-  return s;
-}
-__device__ inline double block_max_n(double v, double* red, int tid, int nwaves) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < nwaves; ++w) s = fmax(s, red[w]);
-  return s;
-}
-// temporal row i (0..74) constrains parameter src(i): rootT, rootAA, then the joints (include/MultiFrameBA.h:121-142)
-__device__ inline int temporal_src(int i) { return (i < 3) ? (4 + i) : (i < 6 ? (1 + (i - 3)) : (7 + (i - 6))); }
-__device__ inline int temporal_row_of(int s) { return (s >= 7) ? (s - 7 + 6) : (s >= 4 ? (s - 4) : (s - 1 + 3)); }   // s >= 1
-
-// dst[i] = src[i], i in [0, n): eight loads in flight per thread and pass (a load-store loop is one dependent round trip per trip)
-__device__ __forceinline__ void copy_batched(double* __restrict__ dst, const double* __restrict__ src, int n, int tid, int nthreads) {
-  int i = tid;
-  for (; i + 7 * nthreads < n; i += 8 * nthreads) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = src[i + u * nthreads];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) dst[i + u * nthreads] = v[u];
-  }
-  for (; i < n; i += nthreads) dst[i] = src[i];
-}
 
 // ---- cost of a residual vector: 1/2 sum rho(|r_kp|^2) over the keypoints + 1/2 |other rows|^2 -----------------------
 __device__ double window_cost(const WinProblem& P, const double* __restrict__ r, double* red, int tid, int nthreads) {
   // independent partial sums per thread, sixteen loads in flight per pass (a 1024-frame window has 170 rows per thread: one
   // dependent load per pass made this the second longest kernel of an iteration, four in flight still left it at 39 us)
+  auto rho = [&](double s) { double rho1; return huber_rho(P.huber, s, &rho1); };   // (the derivative is not needed here)
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   int k = tid;
   for (; k + 7 * nthreads < P.K; k += 8 * nthreads) {
@@ -91,15 +45,15 @@ __device__ double window_cost(const WinProblem& P, const double* __restrict__ r,
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < 8; u += 4) {
-      a0 += 0.5 * huber_rho_w(P.huber, xx[u] * xx[u] + yy[u] * yy[u]);
-      a1 += 0.5 * huber_rho_w(P.huber, xx[u + 1] * xx[u + 1] + yy[u + 1] * yy[u + 1]);
-      a2 += 0.5 * huber_rho_w(P.huber, xx[u + 2] * xx[u + 2] + yy[u + 2] * yy[u + 2]);
-      a3 += 0.5 * huber_rho_w(P.huber, xx[u + 3] * xx[u + 3] + yy[u + 3] * yy[u + 3]);
+      a0 += 0.5 * rho(xx[u] * xx[u] + yy[u] * yy[u]);
+      a1 += 0.5 * rho(xx[u + 1] * xx[u + 1] + yy[u + 1] * yy[u + 1]);
+      a2 += 0.5 * rho(xx[u + 2] * xx[u + 2] + yy[u + 2] * yy[u + 2]);
+      a3 += 0.5 * rho(xx[u + 3] * xx[u + 3] + yy[u + 3] * yy[u + 3]);
     }
   }
   for (; k < P.K; k += nthreads) {
     const double r0 = r[2 * (size_t)k], r1 = r[2 * (size_t)k + 1];
-    a0 += 0.5 * huber_rho_w(P.huber, r0 * r0 + r1 * r1);
+    a0 += 0.5 * rho(r0 * r0 + r1 * r1);
   }
   int i = 2 * P.K + tid;
   for (; i + 15 * nthreads < P.total_rows; i += 16 * nthreads) {
@@ -134,7 +88,7 @@ __global__ __launch_bounds__(1024) void k_win_init(WinProblem P, WinBuf W, const
   if (mode == 2) c = W.fin[0];
   if (threadIdx.x == 0) {
     double* st = W.status;
-    st[kWsCost] = c; st[kWsInitialCost] = c; st[kWsRadius] = 1e4; st[kWsDec] = 2.0; st[kWsModel] = 0.0;
+    st[kWsCost] = c; st[kWsInitialCost] = c; st[kWsRadius] = kLmInitialRadius; st[kWsDec] = kLmInitialDecrease; st[kWsModel] = 0.0;
     st[kWsHasCand] = 0.0; st[kWsIters] = 0.0; st[kWsOk] = 0.0; st[kWsBad] = 0.0;
     const bool finite = (c == c) && c < 1e300;
     st[kWsActive] = finite ? 1.0 : 0.0;
@@ -260,7 +214,7 @@ __global__ __launch_bounds__(kAsmThreads) void k_win_assemble(WinProblem P, WinB
   const int tc = min(tid, NP - 1);
   double g_in = H[(size_t)(NP + NBETA) * kHLd + tc];
   const double rp_in = (P.prior_rows > 0) ? r[P.row_prior + (size_t)f * P.prior_rows + max(tc - 7, 0)] : 0.0;
-  const int ti_c = temporal_row_of(max(tc, 1));
+  const int ti_c = temporal_row(max(tc, 1));
   const double rt_r = (P.lambda_t > 0.0 && pair_right) ? r[P.row_temporal + (size_t)f * 75 + ti_c] : 0.0;
   const double rt_l = (P.lambda_t > 0.0 && f > 0) ? r[P.row_temporal + (size_t)(f - 1) * 75 + ti_c] : 0.0;
   const double xl_in = (f == 0 && x_left) ? x_left[tc] - x[tc] : 0.0;
@@ -369,414 +323,6 @@ __global__ __launch_bounds__(kAsmThreads) void k_win_assemble(WinProblem P, WinB
   if (tid == 0) W.gmaxp[f] = gm;
 }
 
-// Staging of 80 x 80 (or 16 x 80) blocks between HBM/L2 and LDS.  A plain `for (idx = tid; idx < n; idx += threads) lds[..] =
-// g[idx]` compiles to load -> s_waitcnt vmcnt(0) -> ds_write per trip: thirteen DEPENDENT L2 round trips per block (k_cr_factor
-// spent 9 of its 27 us in them).  Here every load of a block is issued before the first is used (fixed trip count, clamped
-// index, predicated use).
-constexpr int kCrThreads = 512, kCrWaves = 8;
-template <int ROWS>
-struct BlockRegs { static constexpr int kPasses = (ROWS * WB + kCrThreads - 1) / kCrThreads; double v[kPasses]; };
-template <int ROWS>
-__device__ __forceinline__ void block_load(BlockRegs<ROWS>& r, const double* __restrict__ src, int tid) {
-#pragma unroll
-  for (int u = 0; u < BlockRegs<ROWS>::kPasses; ++u) r.v[u] = src[min(tid + u * kCrThreads, ROWS * WB - 1)];
-}
-// dst[row][col] (leading dimension LD); transposed: the element (i, k) of the source lands at row k, column i
-template <int ROWS, bool kTransposed = false, bool kLowerOnly = false>
-__device__ __forceinline__ void block_to_lds(const BlockRegs<ROWS>& r, double* dst, int tid) {
-#pragma unroll
-  for (int u = 0; u < BlockRegs<ROWS>::kPasses; ++u) {
-    const int idx = tid + u * kCrThreads;
-    if (idx < ROWS * WB) {
-      const int i = idx / WB, k = idx % WB;
-      const double v = (kLowerOnly && k > i) ? 0.0 : r.v[u];
-      dst[kTransposed ? k * LD + i : i * LD + k] = v;
-    }
-  }
-}
-// LDS [ROWS][LD] -> global [ROWS][WB]: the LDS reads of the block first, then its stores
-template <int ROWS, bool kLowerOnly = false>
-__device__ __forceinline__ void block_from_lds(double* __restrict__ dst, const double* src, int tid) {
-  BlockRegs<ROWS> r;
-#pragma unroll
-  for (int u = 0; u < BlockRegs<ROWS>::kPasses; ++u) {
-    const int idx = min(tid + u * kCrThreads, ROWS * WB - 1);
-    r.v[u] = src[(idx / WB) * LD + idx % WB];
-  }
-#pragma unroll
-  for (int u = 0; u < BlockRegs<ROWS>::kPasses; ++u) {
-    const int idx = tid + u * kCrThreads;
-    if (idx < ROWS * WB) dst[idx] = (kLowerOnly && idx % WB > idx / WB) ? 0.0 : r.v[u];
-  }
-}
-
-// ---- cyclic reduction: factor one eliminated block, solve its appended rows -------------------------------------------
-// Two workgroups per eliminated frame j (side = blockIdx.x & 1): both factor D_j = L L^T (right-looking, 16-column
-// panels, the k_lm_step scheme: diagonal block in the registers of wave 0, panel solve one row per thread, trailing update
-// on the f64 matrix cores) with rows appended below that receive L^-T from the right:
-//   side 0:  rows of U_a (-> Pt_j)  and the 16 rows of Rt_j (-> Yt_j);  writes L_j
-//   side 1:  rows of U_j^T (-> Qt_j)
-constexpr int kCrRowsMax = WB + WB + WR;   // 176
-#ifdef BODYFIT_CR_STAMPS   // diagnostic build only (tools/ubench/cr_factor_phases.hip): s_memtime of wave 0 per phase
-__device__ unsigned long long g_cr_stamps[64];
-#define CR_STAMP(i)                                                                   \
-  do {                                                                                \
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                                        \
-      unsigned long long t_;                                                          \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");     \
-      g_cr_stamps[i] = t_;                                                            \
-    }                                                                                 \
-  } while (0)
-#else
-#define CR_STAMP(i)
-#endif
-// (the pointers of the kernel's first loads come as leading scalar arguments: with -mllvm -amdgpu-kernarg-preload-count they are
-//  in SGPRs when the wave starts, one scalar round trip earlier than fields of the by-value struct)
-__global__ __launch_bounds__(kCrThreads) void k_cr_factor(const int* __restrict__ elim, const double* __restrict__ Dp,
-                                                          const double* __restrict__ Up, const double* __restrict__ Rtp,
-                                                          int n_elim, WinBuf W) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* M = sm;                          // [kCrRowsMax][LD]
-  double* invd = sm + kCrRowsMax * LD;     // [WB]
-  double* stat = invd + WB;                // [1]
-  const int e = blockIdx.x >> 1, side = blockIdx.x & 1;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int j = elim[3 * e], a = elim[3 * e + 1], b = elim[3 * e + 2];
-  if (side == 1 && b < 0) return;
-  CR_STAMP(0);
-  const int nU = (side == 0) ? (a >= 0 ? WB : 0) : WB;       // appended coupling rows
-  const int nApp = nU + (side == 0 ? WR : 0);
-  const int nRows = WB + nApp;
-  {
-    // the node's blocks: all three requested before any lands in LDS (one round trip)
-    BlockRegs<WB> rD, rU;
-    BlockRegs<WR> rR;
-    block_load<WB>(rD, Dp + (size_t)j * WB * WB, tid);
-    if (nU) block_load<WB>(rU, Up + (size_t)(side == 0 ? a : j) * WB * WB, tid);
-    if (side == 0) block_load<WR>(rR, Rtp + (size_t)j * WR * WB, tid);
-    block_to_lds<WB, false, true>(rD, M, tid);
-    if (nU) {
-      if (side == 0) block_to_lds<WB>(rU, M + WB * LD, tid);              // row i of U_a
-      else block_to_lds<WB, true>(rU, M + WB * LD, tid);                  // row i of U_j^T = column i of U_j
-    }
-    if (side == 0) block_to_lds<WR>(rR, M + (WB + nU) * LD, tid);
-  }
-  if (tid == 0) stat[0] = 1.0;
-  __syncthreads();
-  CR_STAMP(1);
-  constexpr int NPAN = WB / 16;   // 5
-  double* Linv = stat + 8;        // [16][17]: L_pp^-T of the current panel
-  // (a) diagonal block p + identity below it, in the registers of wave 0, spread over all 64 lanes in the layout of an f64
-  //     16 x 16 accumulator (dense_inl.h diag_factor16_acc): lane (m, kk), register q <-> row kk + 4 q, column m
-  auto diag_block = [&](int p) {
-    const int c0 = 16 * p;
-    const int m = lane & 15, kk = lane >> 4;
-    double av[4], bv[4], invc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {   // (the FULL symmetric block: only its lower triangle is kept up to date in LDS, mirror it)
-      const int r = kk + 4 * q, lo = max(r, m), hi = min(r, m);
-      av[q] = M[(c0 + lo) * LD + c0 + hi];
-      bv[q] = (r == m) ? 1.0 : 0.0;
-    }
-    const bool okp = diag_factor16_acc(av, bv, lane, invc, min(16, NP - c0));
-    double* Lg = W.Li + ((size_t)j * (WB / 16) + p) * 256;   // kept for the way down (k_cr_back)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = kk + 4 * q;
-      if (r >= m) M[(c0 + r) * LD + c0 + m] = av[q];           // L (lower triangle)
-      Linv[r * 17 + m] = bv[q];                                // row r of L_pp^-T (zero left of the diagonal)
-      if (side == 0) Lg[r * 16 + m] = bv[q];
-    }
-    if (lane == 0 && !okp) stat[0] = 0.0;
-  };
-  if (wave == 0) diag_block(0);
-  __syncthreads();
-  CR_STAMP(2);
-  const int nRowTiles = nRows / 16;
-  for (int p = 0; p < NPAN; ++p) {
-    const int c0 = 16 * p;
-    // (b) panel solve on the matrix cores: every 16-row tile below the diagonal block  X = A L_pp^-T
-    {
-      const int m = lane & 15, kk = lane >> 4;
-      for (int I = p + 1 + wave; I < nRowTiles; I += kCrWaves) {
-        double a4[4];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) a4[s4] = M[(16 * I + m) * LD + c0 + 4 * s4 + kk];
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[s4], Linv[(4 * s4 + kk) * 17 + m], acc, 0, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) M[(16 * I + kk + 4 * q) * LD + c0 + m] = acc[q];
-      }
-    }
-    __syncthreads();
-    CR_STAMP(3 + 4 * p);
-    // (c) trailing update on the matrix cores: rows of tile I, columns of panel Kc > p:  M[I][Kc] -= X_I X_Kc^T.
-    //     Look-ahead: wave 0 updates the next diagonal tile first and factors it at once (the serial part of a panel)
-    //     while the other seven waves update the rest.
-    if (p + 1 < NPAN) {
-      const int m = lane & 15, kk = lane >> 4;
-      auto tile_update = [&](int I, int Kc) {
-        d4 acc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = M[(16 * I + kk + 4 * q) * LD + 16 * Kc + m];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          const double av = -M[(16 * I + m) * LD + c0 + 4 * s4 + kk];
-          const double bv = M[(16 * Kc + m) * LD + c0 + 4 * s4 + kk];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) M[(16 * I + kk + 4 * q) * LD + 16 * Kc + m] = acc[q];
-      };
-      // a whole row of tiles per wave: the row tile's own panel entries (A operand) are read once, every LDS read of the row
-      // is issued before the first product, and the <= 4 column tiles are four independent accumulator chains (tile by tile,
-      // each product waited for its two LDS reads and the previous product: ~790 cycles per tile against 256 of matrix work)
-      auto row_update = [&](int I) {
-        const int kc1 = (I < NPAN) ? I : NPAN - 1;                 // last column tile of this row
-        double a4[4];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) a4[s4] = -M[(16 * I + m) * LD + c0 + 4 * s4 + kk];
-        d4 acc[4];
-        double b4[4][4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int Kc = min(p + 1 + j, NPAN - 1);                 // (clamped: loads of unused tiles stay inside the block)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[j][q] = M[(16 * I + kk + 4 * q) * LD + 16 * Kc + m];
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) b4[j][s4] = M[(16 * Kc + m) * LD + c0 + 4 * s4 + kk];
-        }
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (p + 1 + j <= kc1) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[s4], b4[j][s4], acc[j], 0, 0, 0);   // (uniform)
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (p + 1 + j <= kc1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) M[(16 * I + kk + 4 * q) * LD + 16 * (p + 1 + j) + m] = acc[j][q];
-          }
-        }
-      };
-      if (wave == 0) {
-        tile_update(p + 1, p + 1);
-        CR_STAMP(4 + 4 * p);
-        diag_block(p + 1);
-        CR_STAMP(5 + 4 * p);
-      } else {
-        for (int I = p + 2 + (wave - 1); I < nRowTiles; I += kCrWaves - 1) row_update(I);
-      }
-    }
-    __syncthreads();
-    CR_STAMP(6 + 4 * p);
-  }
-  if (tid == 0 && stat[0] == 0.0) *W.fail = 1;
-  if (side == 0) {
-    block_from_lds<WB, true>(W.L + (size_t)j * WB * WB, M, tid);
-    if (nU) block_from_lds<WB>(W.Pt + (size_t)j * WB * WB, M + WB * LD, tid);
-    block_from_lds<WR>(W.Yt + (size_t)j * WR * WB, M + (WB + nU) * LD, tid);
-  } else {
-    block_from_lds<WB>(W.Qt + (size_t)j * WB * WB, M + WB * LD, tid);
-  }
-  CR_STAMP(24);
-}
-
-// C[ti][tj] (16 x 16 tile, accumulator layout: row = (lane >> 4) + 4 q, column = lane & 15) += sign * sum_k X[i][k] Y[i'][k]
-// with X, Y staged in LDS (leading dimension LD), K = WB
-__device__ __forceinline__ d4 tile_xyT(const double* X, const double* Y, int ti, int tj, int lane, d4 acc, double sign) {
-  const int m = lane & 15, kk = lane >> 4;
-#pragma unroll 4
-  for (int s = 0; s < WB / 4; ++s) {
-    const double av = sign * X[(16 * ti + m) * LD + 4 * s + kk];
-    const double bv = Y[(16 * tj + m) * LD + 4 * s + kk];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// ---- cyclic reduction: Schur updates of one remaining frame a (left eliminated neighbour jl, right one jr, next
-//      remaining frame b).  Four workgroups per frame: diagonal block (two halves of its tiles), coupling block, rhs. -----
-__global__ __launch_bounds__(kCrThreads) void k_cr_update(const int* __restrict__ surv, int n_surv, int split,
-                                                          double* __restrict__ Dp, const double* __restrict__ Qtp,
-                                                          const double* __restrict__ Ptp, WinBuf W) {   // (leading scalars: k_cr_factor)
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* X0 = sm;                 // [WB][LD]
-  double* X1 = sm + WB * LD;       // [WB][LD]
-  double* Ys = X1 + WB * LD;       // [2][WR][LD]
-  // four workgroups per remaining frame: the diagonal block's 15 lower tiles in two halves (its 600 f64 matrix
-  // instructions were the longest part by 2x: one tile per wave now), the coupling block, the right-hand sides
-  // (split = 1, levels that do not fill the chip; on the throughput-bound levels of a long window one workgroup takes both
-  //  halves: three workgroups per frame)
-  const int sidx = split ? (int)(blockIdx.x >> 2) : (int)(blockIdx.x / 3), part4 = split ? (int)(blockIdx.x & 3) : -1;
-  const int part = split ? (part4 < 2 ? 0 : part4 - 1) : (int)(blockIdx.x % 3);
-  const int h0 = split ? (part4 & 1) : 0, h1 = split ? h0 + 1 : 2;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int a = surv[4 * sidx], jl = surv[4 * sidx + 1], jr = surv[4 * sidx + 2], b = surv[4 * sidx + 3];
-  const int m = lane & 15, kk = lane >> 4;
-  // Every operand of the part is requested before the first is used: the source blocks (13 loads per thread each) and the
-  // accumulator tiles of the wave (read-modify-write of global memory), one round trip instead of one per trip / per tile.
-  if (part == 0) {
-    // D_a -= Qt_jl Qt_jl^T + Pt_jr Pt_jr^T  (15 lower tiles over 8 waves: tiles wave and wave + 8)
-    double* D = Dp + (size_t)a * WB * WB;
-    BlockRegs<WB> r0, r1;
-    if (jl >= 0) block_load<WB>(r0, Qtp + (size_t)jl * WB * WB, tid);
-    if (jr >= 0) block_load<WB>(r1, Ptp + (size_t)jr * WB * WB, tid);
-    int tis[2], tjs[2];
-    d4 acc[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {                         // this wave's tile of each half it carries
-      const int t = min(wave + 8 * u, 14);
-      int ti = 0, tj = t;
-      while (tj > ti) { tj -= ti + 1; ++ti; }             // t -> (ti, tj) of the lower triangle, row-major
-      tis[u] = ti; tjs[u] = tj;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[u][q] = (u >= h0 && u < h1) ? D[(size_t)(16 * ti + kk + 4 * q) * WB + 16 * tj + m] : 0.0;
-    }
-    if (jl >= 0) block_to_lds<WB>(r0, X0, tid);
-    if (jr >= 0) block_to_lds<WB>(r1, X1, tid);
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (u < h0 || u >= h1 || wave + 8 * u > 14) continue;
-      // the two sources as two independent accumulator chains
-      d4 acc2 = {0.0, 0.0, 0.0, 0.0};
-      if (jl >= 0) acc[u] = tile_xyT(X0, X0, tis[u], tjs[u], lane, acc[u], -1.0);
-      if (jr >= 0) acc2 = tile_xyT(X1, X1, tis[u], tjs[u], lane, acc2, -1.0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) D[(size_t)(16 * tis[u] + kk + 4 * q) * WB + 16 * tjs[u] + m] = acc[u][q] + acc2[q];
-    }
-  } else if (part == 1) {
-    // U_a := -Pt_jr Qt_jr^T  (coupling of a with the next remaining frame b)
-    if (jr < 0 || b < 0) return;
-    BlockRegs<WB> r0, r1;
-    block_load<WB>(r0, W.Pt + (size_t)jr * WB * WB, tid);
-    block_load<WB>(r1, W.Qt + (size_t)jr * WB * WB, tid);
-    block_to_lds<WB>(r0, X0, tid);
-    block_to_lds<WB>(r1, X1, tid);
-    __syncthreads();
-    double* U = W.U + (size_t)a * WB * WB;
-    for (int t = wave; t < 25; t += kCrWaves) {
-      const int ti = t / 5, tj = t % 5;
-      d4 acc = {0.0, 0.0, 0.0, 0.0};
-      acc = tile_xyT(X0, X1, ti, tj, lane, acc, -1.0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) U[(size_t)(16 * ti + kk + 4 * q) * WB + 16 * tj + m] = acc[q];
-    }
-  } else {
-    // Rt_a -= Yt_jl Qt_jl^T + Yt_jr Pt_jr^T   ([16 x 80]: one column tile per wave, waves 0-4)
-    double* Rt = W.Rt + (size_t)a * WR * WB;
-    BlockRegs<WB> r0, r1;
-    BlockRegs<WR> y0, y1;
-    if (jl >= 0) { block_load<WB>(r0, W.Qt + (size_t)jl * WB * WB, tid); block_load<WR>(y0, W.Yt + (size_t)jl * WR * WB, tid); }
-    if (jr >= 0) { block_load<WB>(r1, W.Pt + (size_t)jr * WB * WB, tid); block_load<WR>(y1, W.Yt + (size_t)jr * WR * WB, tid); }
-    const int tj = min(wave, 4);
-    d4 acc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = Rt[(size_t)(kk + 4 * q) * WB + 16 * tj + m];
-    if (jl >= 0) { block_to_lds<WB>(r0, X0, tid); block_to_lds<WR>(y0, Ys, tid); }
-    if (jr >= 0) { block_to_lds<WB>(r1, X1, tid); block_to_lds<WR>(y1, Ys + WR * LD, tid); }
-    __syncthreads();
-    if (wave < 5) {
-      if (jl >= 0) acc = tile_xyT(Ys, X0, 0, tj, lane, acc, -1.0);
-      if (jr >= 0) acc = tile_xyT(Ys + WR * LD, X1, 0, tj, lane, acc, -1.0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Rt[(size_t)(kk + 4 * q) * WB + 16 * tj + m] = acc[q];
-    }
-  }
-}
-
-// ---- cyclic reduction, way down: x_j = L_j^-T (Y_j - P_j x_a - Q_j x_b), 11 right-hand sides ---------------------------
-// In the transposed storage:  Zt = Yt - Xt_a Pt - Xt_b Qt  ([16 x 80] = [16 x 80][80 x 80], f64 MFMA, B operands straight from
-// L2: 16 consecutive doubles per lane group), then  Xt L = Zt  solved panel by panel from the last one: the products with
-// the already known panels on the matrix cores, the 16 x 16 diagonal blocks through their explicit inverses (computed
-// here, one block per wave, while the other waves form Zt).
-__global__ __launch_bounds__(kCrThreads) void k_cr_back(const int* __restrict__ elim, const double* __restrict__ Lp,
-                                                        const double* __restrict__ Xtp, int n_elim, WinBuf W) {   // (leading scalars: k_cr_factor)
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* Ls = sm;                     // [WB][LD]
-  double* Zt = sm + WB * LD;           // [WR][LD]   right-hand sides, overwritten by the solution panel by panel
-  double* Xa = Zt + WR * LD;           // [WR][LD]
-  double* Xb = Xa + WR * LD;           // [WR][LD]
-  double* Li = Xb + WR * LD;           // [5][16][17]  inverses of the diagonal blocks of L
-  const int e = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int m = lane & 15, kk = lane >> 4;
-  const int j = elim[3 * e], a = elim[3 * e + 1], b = elim[3 * e + 2];
-  {
-    BlockRegs<WB> rL;
-    BlockRegs<WR> rA, rB;
-    block_load<WB>(rL, Lp + (size_t)j * WB * WB, tid);
-    if (a >= 0) block_load<WR>(rA, Xtp + (size_t)a * WR * WB, tid);
-    if (b >= 0) block_load<WR>(rB, Xtp + (size_t)b * WR * WB, tid);
-    block_to_lds<WB>(rL, Ls, tid);
-    if (a >= 0) block_to_lds<WR>(rA, Xa, tid);
-    if (b >= 0) block_to_lds<WR>(rB, Xb, tid);
-  }
-  __syncthreads();
-  if (wave < 5) {
-    // Zt tile (all 16 rows, columns 16 wave ..): accumulate -X P and -X Q on top of Yt
-    const int tj = wave;
-    const double* Yt = W.Yt + (size_t)j * WR * WB;
-    d4 acc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = Yt[(size_t)(kk + 4 * q) * WB + 16 * tj + m];
-    for (int src = 0; src < 2; ++src) {
-      const int nb_ = src == 0 ? a : b;
-      if (nb_ < 0) continue;
-      const double* G = (src == 0 ? W.Pt : W.Qt) + (size_t)j * WB * WB;
-      const double* Xs = src == 0 ? Xa : Xb;
-      double bv[WB / 4];
-#pragma unroll
-      for (int s4 = 0; s4 < WB / 4; ++s4) bv[s4] = G[(size_t)(4 * s4 + kk) * WB + 16 * tj + m];
-#pragma unroll
-      for (int s4 = 0; s4 < WB / 4; ++s4)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-Xs[m * LD + 4 * s4 + kk], bv[s4], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) Zt[(kk + 4 * q) * LD + 16 * tj + m] = acc[q];
-  } else if (wave == 5 || wave == 6) {
-    // inverses of the five 16 x 16 diagonal blocks of L, as k_cr_factor left them: (L_pp^-T)[c][r] = (L_pp^-1)[r][c]
-    const double* Lg = W.Li + (size_t)j * (WB / 16) * 256;
-    for (int it = tid - 320; it < 5 * 256; it += 128) {
-      const int blk = it >> 8, c = (it >> 4) & 15, r = it & 15;
-      Li[(blk * 16 + r) * 17 + c] = Lg[it];
-    }
-  }
-  __syncthreads();
-  // Xt[:, p] = (Zt[:, p] - sum_{q > p} Xt[:, q] L[q, p]) Linv_pp, panels from the last to the first; wave 0 only (each step
-  // depends on the previous one; 4 + 4 (5 - p - 1) MFMAs per step)
-  if (wave == 0) {
-    for (int p = 4; p >= 0; --p) {
-      d4 acc;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = Zt[(kk + 4 * q) * LD + 16 * p + m];
-      for (int qp = p + 1; qp < 5; ++qp) {
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-Zt[m * LD + 16 * qp + 4 * s4 + kk], Ls[(16 * qp + 4 * s4 + kk) * LD + 16 * p + m],
-                                                     acc, 0, 0, 0);
-      }
-      // through LDS: the accumulator tile becomes the A operand of the product with the inverse
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Zt[(kk + 4 * q) * LD + 16 * p + m] = acc[q];
-      d4 xo = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4)
-        xo = __builtin_amdgcn_mfma_f64_16x16x4f64(Zt[m * LD + 16 * p + 4 * s4 + kk], Li[(p * 16 + 4 * s4 + kk) * 17 + m], xo, 0, 0, 0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Zt[(kk + 4 * q) * LD + 16 * p + m] = xo[q];
-    }
-  }
-  __syncthreads();
-  double* Xt = W.Xt + (size_t)j * WR * WB;
-  for (int idx = tid; idx < WR * WB; idx += kCrThreads) {
-    const int c = idx / WB, k = idx % WB;
-    Xt[idx] = (c <= NBETA) ? Zt[c * LD + k] : 0.0;
-  }
-}
-
 // ---- beta Schur complement: per-frame partials, then the 10 x 10 solve ---------------------------------------------------
 __global__ __launch_bounds__(128) void k_win_schur_part(WinProblem P, WinBuf W) {
   __shared__ double sBt[(NBETA + 1) * WB], sXt[(NBETA + 1) * WB];
@@ -855,7 +401,7 @@ __global__ __launch_bounds__(1024) void k_win_beta_solve(WinProblem P, WinBuf W,
     const bool ok = diag_factor16(av, rr, grp == 0, iv, NBETA);
     double x = 0.0;
 #pragma unroll
-    for (int k = 0; k < NBETA; ++k) x += av[k] * readlane_f64w(av[k], 16);     // lanes 32 + r: sum_k (L^-T)[r][k] y[k]
+    for (int k = 0; k < NBETA; ++k) x += av[k] * readlane_f64(av[k], 16);     // lanes 32 + r: sum_k (L^-T)[r][k] y[k]
     if (grp == 2 && rr < NBETA) {
       const double dsb = ok ? x : 0.0;
       W.dsb[rr] = dsb;
@@ -932,64 +478,6 @@ __global__ __launch_bounds__(128) void k_win_model(WinProblem P, WinBuf W, const
   if (tid == 0) {
     double* o = W.part + (size_t)f * kWinPart + 112;
     o[0] = pm; o[1] = dn; o[2] = xn;
-  }
-}
-
-// ---- decide: gradient tolerance, failed factorisation, parameter tolerance, or a candidate --------------------------------
-// mode 0: all; 1: this shard's sums -> W.fin[0..3] = {model, |d|^2, |x|^2, max |g_frames|}, W.fin[4] = fail flag, only;
-// 2: decide from W.fin (the first three summed, the last two maximised over the shards)
-// the decision of an iteration from the sums over the frames (256 threads): gradient tolerance, failed factorisation,
-// parameter tolerance, or a candidate
-__device__ __forceinline__ void finish_core(const WinProblem& P, const WinBuf& W, const double* __restrict__ x,
-                                            const double* __restrict__ beta, double* __restrict__ x_new,
-                                            double* __restrict__ beta_new, double pm, double dn, double xn, double gm, int tid) {
-  const int F = P.F;
-  if (tid == 0) gm = fmax(gm, W.gmaxp[F]);
-  // the beta block's operands into LDS first (one round trip; thread 0 walking global memory made this an 11 us kernel)
-  __shared__ double sCr[NBETA * NBETA], sdb2[NBETA], sgb[NBETA], sbt[NBETA];
-  if (tid < NBETA * NBETA) sCr[tid] = W.Craw[tid];
-  if (tid >= 128 && tid < 128 + NBETA) {
-    const int a = tid - 128;
-    sdb2[a] = (a < P.nb) ? W.d[(size_t)F * NP + a] : 0.0;
-    sgb[a] = W.gbraw[a];
-    sbt[a] = (a < P.nb) ? beta[a] : 0.0;
-  }
-  __syncthreads();
-  __shared__ int no_cand;
-  if (tid == 0) {
-    double* st = W.status;
-    for (int a = 0; a < P.nb; ++a) {
-      const double da = sdb2[a];
-      pm -= da * sgb[a];
-      double h = 0.0;
-      for (int c = 0; c < P.nb; ++c) h += sCr[a * NBETA + c] * sdb2[c];
-      pm -= 0.5 * da * h;
-      dn += da * da;
-      xn += sbt[a] * sbt[a];
-    }
-    st[kWsGmax] = gm;
-    st[kWsHasCand] = 0.0;
-    no_cand = 1;
-    if (st[kWsActive] != 0.0) {
-      if (gm <= 1e-10) {                                   // Ceres gradient_tolerance
-        st[kWsActive] = 0.0; st[kWsTermination] = 0.0;
-      } else if (*W.fail) {                                // the damped system was not positive definite
-        const double rad = st[kWsRadius] / st[kWsDec];
-        st[kWsRadius] = rad; st[kWsDec] *= 2.0; st[kWsBad] += 1.0; st[kWsIters] += 1.0;
-        st[kWsAccepted] = 0.0;
-        if (rad < 1e-32) { st[kWsActive] = 0.0; st[kWsTermination] = 2.0; }
-      } else if (sqrt(dn) <= 1e-8 * (sqrt(xn) + 1e-8)) {   // Ceres parameter_tolerance
-        st[kWsActive] = 0.0; st[kWsTermination] = 0.0;
-      } else {
-        st[kWsModel] = pm; st[kWsHasCand] = 1.0;
-        no_cand = 0;
-      }
-    }
-  }
-  __syncthreads();
-  if (no_cand) {   // the residual sweep that follows still reads a well-defined point
-    copy_batched(x_new, x, F * NP, tid, 256);
-    if (tid < P.nb) beta_new[tid] = beta[tid];
   }
 }
 
@@ -1126,44 +614,6 @@ __global__ __launch_bounds__(256) void k_win_tail(WinProblem P, WinBuf W, const 
   finish_core(P, W, x, beta, x_new, beta_new, pm, dn, xn, gm, tid);
 }
 
-// ---- accept / reject the candidate (Ceres' step quality and radius rules, host_solver.cpp) ------------------------------
-// the decision itself, for a candidate that exists (status HasCand), given the candidate's cost; thread 0 decides, every
-// thread then copies the accepted point.  Returns (to every thread) whether the candidate was accepted.
-__device__ __forceinline__ bool accept_core(const WinProblem& P, const WinBuf& W, double* __restrict__ x, double* __restrict__ beta,
-                                            const double* __restrict__ x_new, const double* __restrict__ beta_new, double new_cost,
-                                            int tid, int nthreads) {
-  __shared__ int acc_flag;
-  double* st = W.status;
-  if (tid == 0) {
-    const double cost = st[kWsCost], model = st[kWsModel];
-    const double change = cost - new_cost, rho = change / model;
-    const bool accept = (new_cost == new_cost) && new_cost < 1e300 && model > 0.0 && rho > 1e-3;
-    st[kWsIters] += 1.0;
-    st[kWsNewCost] = new_cost;
-    if (accept) {
-      st[kWsCost] = new_cost;
-      const double t = 2.0 * rho - 1.0;
-      st[kWsRadius] = fmin(1e16, st[kWsRadius] / fmax(1.0 / 3.0, 1.0 - t * t * t));
-      st[kWsDec] = 2.0;
-      st[kWsOk] += 1.0;
-      if (fabs(change) < 1e-6 * cost) { st[kWsActive] = 0.0; st[kWsTermination] = 0.0; }   // function_tolerance
-    } else {
-      const double rad = st[kWsRadius] / st[kWsDec];
-      st[kWsRadius] = rad; st[kWsDec] *= 2.0; st[kWsBad] += 1.0;
-      if (rad < 1e-32) { st[kWsActive] = 0.0; st[kWsTermination] = 2.0; }
-    }
-    st[kWsAccepted] = accept ? 1.0 : 0.0;
-    st[kWsJsel] = accept ? 1.0 : 2.0;     // (single-GPU loop: the candidate sweep also left the candidate's Jacobian)
-    st[kWsHasCand] = 0.0;
-    acc_flag = accept ? 1 : 0;
-  }
-  __syncthreads();
-  if (acc_flag) {
-    copy_batched(x, x_new, P.F * NP, tid, nthreads);
-    if (tid < P.nb) beta[tid] = beta_new[tid];
-  }
-  return acc_flag != 0;
-}
 // mode 0: all; 1: this shard's cost at the candidate -> W.fin[0] only; 2: decide with W.fin[0] (summed over the shards);
 // 3: this shard's cost at the candidate -> W.fin[5] only (sharded solves: the decision is k_win_decide's)
 __global__ __launch_bounds__(1024) void k_win_accept(WinProblem P, WinBuf W, const double* __restrict__ r_new,
@@ -1186,143 +636,7 @@ __global__ __launch_bounds__(1024) void k_win_accept(WinProblem P, WinBuf W, con
   (void)accept_core(P, W, x, beta, x_new, beta_new, new_cost, tid, 1024);
 }
 
-// ---- sharded solves (bodyfit_solve_sharded*): what the exchanges need ----------------------------------------------------
-// sum of the shards' partials in rank order: out[i] = sum_r gathered[r][i] (every rank computes bit-identical totals)
-__global__ __launch_bounds__(256) void k_sum_ranks(const double* __restrict__ g, int N, int stride, int n, double* __restrict__ out) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    double s = 0.0;
-    for (int r = 0; r < N; ++r) s += g[(size_t)r * stride + i];
-    out[i] = s;
-  }
-}
-// shard proxy (bodyfit_set_shard_proxy, a measurement aid): the one-rank all-gather has filled slot 0; the other N - 1 slots
-// get copies, as if N identical shards had contributed
-__global__ __launch_bounds__(256) void k_replicate_ranks(double* __restrict__ g, int n, int N) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const double v = g[i];
-    for (int r = 1; r < N; ++r) g[(size_t)r * n + i] = v;
-  }
-}
-// this shard's contribution to the interface system: [D_first, D_last, U_first, U_last | Rt_first, Rt_last | extra], one
-// contiguous buffer for ONE all-gather
-__global__ __launch_bounds__(256) void k_iface_pack(WinBuf W, int F, const double* __restrict__ extra, int n_extra,
-                                                    double* __restrict__ send) {
-  constexpr int blk = WB * WB, rhs = WR * WB;
-  const int fl = F - 1, total = 4 * blk + 2 * rhs + n_extra;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    double v;
-    if (i < blk) v = W.D[i];
-    else if (i < 2 * blk) v = W.D[(size_t)fl * blk + (i - blk)];
-    else if (i < 3 * blk) v = W.U[i - 2 * blk];
-    else if (i < 4 * blk) v = W.U[(size_t)fl * blk + (i - 3 * blk)];
-    else if (i < 4 * blk + rhs) v = W.Rt[i - 4 * blk];
-    else if (i < 4 * blk + 2 * rhs) v = W.Rt[(size_t)fl * rhs + (i - 4 * blk - rhs)];
-    else v = extra[i - 4 * blk - 2 * rhs];
-    send[i] = v;
-  }
-}
-// the gathered contributions -> the interface chain of 2 N frames (every rank builds the same), the extras summed in rank order
-__global__ __launch_bounds__(256) void k_iface_unpack(WinBuf Wi, const double* __restrict__ g, int N, int n_extra,
-                                                      double* __restrict__ extra_sum) {
-  constexpr int blk = WB * WB, rhs = WR * WB;
-  const int per = 4 * blk + 2 * rhs + n_extra;
-  const int total = N * (4 * blk + 2 * rhs) + n_extra;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    if (i < N * (4 * blk + 2 * rhs)) {
-      const int r = i / (4 * blk + 2 * rhs), j = i - r * (4 * blk + 2 * rhs);
-      const double v = g[(size_t)r * per + j];
-      if (j < 2 * blk) Wi.D[(size_t)(2 * r) * blk + j] = v;
-      else if (j < 4 * blk) Wi.U[(size_t)(2 * r) * blk + (j - 2 * blk)] = v;
-      else Wi.Rt[(size_t)(2 * r) * rhs + (j - 4 * blk)] = v;
-    } else {
-      const int e = i - N * (4 * blk + 2 * rhs);
-      double s = 0.0;
-      for (int r = 0; r < N; ++r) s += g[(size_t)r * per + 4 * blk + 2 * rhs + e];
-      extra_sum[e] = s;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *Wi.fail = 0;
-}
-// The steps of the neighbouring shards' boundary frames, computed HERE from the interface solution every rank holds (node
-// 2 r = first frame of shard r, 2 r + 1 = its last): the same arithmetic as k_win_step on the same numbers, so the row this
-// rank keeps of its neighbour's frame is bit-identical to the neighbour's own.  block 0: the next shard's first frame (the
-// halo row of the temporal pair this shard owns), block 1: the previous shard's last frame.
-__global__ __launch_bounds__(128) void k_win_halo_step(WinProblem P, const double* __restrict__ Xi, const double* __restrict__ dsb,
-                                                       int node_right, const double* __restrict__ scale_right,
-                                                       const double* __restrict__ x_right, double* __restrict__ d_right,
-                                                       double* __restrict__ xn_right, int node_left,
-                                                       const double* __restrict__ scale_left, const double* __restrict__ x_left,
-                                                       double* __restrict__ xn_left) {
-  const int tid = threadIdx.x;
-  if (tid >= NP) return;
-  const bool right = blockIdx.x == 0;
-  const int node = right ? node_right : node_left;
-  if (node < 0) return;
-  const double* X = Xi + (size_t)node * WR * WB;
-  double ds = X[NBETA * WB + tid];
-#pragma unroll
-  for (int c = 0; c < NBETA; ++c) ds -= (c < P.nb) ? X[c * WB + tid] * dsb[c] : 0.0;
-  const double sc = (right ? scale_right : scale_left)[tid];
-  const double xi = (right ? x_right : x_left)[tid];
-  double di = ds * sc;
-  if (tid == 0) {
-    const double s_new = fmin(fmax(xi + di, P.scale_lo), P.scale_hi);
-    di = s_new - xi;
-  }
-  if (right) { d_right[tid] = di; xn_right[tid] = xi + di; }
-  else xn_left[tid] = xi + di;
-}
-// a failed interface factorisation (every rank factors the same chain) is this shard's failure too
-__global__ void k_win_fold_fail(WinBuf W, WinBuf Wi) {
-  if (threadIdx.x == 0 && *Wi.fail) *W.fail = 1;
-}
-// The whole decision of a sharded iteration in one launch, from every shard's partials [model, |d|^2, |x|^2, max |g|, fail,
-// cost at the candidate] (gathered, [N][8]): k_win_finish's tests, then — if there is a candidate — k_win_accept's.  Every
-// rank runs it on the same numbers.  On acceptance the rows this rank keeps of its neighbours' boundary frames move too.
-__global__ __launch_bounds__(256) void k_win_decide(WinProblem P, WinBuf W, double* __restrict__ x, double* __restrict__ beta,
-                                                    double* __restrict__ x_new, double* __restrict__ beta_new,
-                                                    const double* __restrict__ g, int N, double* __restrict__ x_halo,
-                                                    const double* __restrict__ xn_halo, double* __restrict__ x_left,
-                                                    const double* __restrict__ xn_left) {
-  const int tid = threadIdx.x;
-  double pm = 0.0, dn = 0.0, xn = 0.0, gm = 0.0, fl = 0.0, cost = 0.0, poison = 0.0;
-  for (int r = 0; r < N; ++r) {
-    const double* o = g + (size_t)r * 8;
-    pm += o[0]; dn += o[1]; xn += o[2];
-    gm = fmax(gm, o[3]); fl = fmax(fl, o[4]);
-    cost += o[5];
-    poison = fmax(poison, o[6]);
-  }
-  if (poison != 0.0) {
-    // A rank could not produce its part of this iteration (a failed launch / HIP call: api_solve.hip puts a 1 in slot 6 of its
-    // scalars and keeps taking part in the exchanges).  Every rank reads the same gathered scalars, so every rank ends the solve
-    // HERE, in the same iteration: nothing moves, the host loops find the solve inactive at their next status read and return.
-    if (tid == 0) {
-      W.status[kWsActive] = 0.0; W.status[kWsTermination] = 2.0; W.status[kWsHasCand] = 0.0; W.status[kWsJsel] = 2.0;
-      W.status[kWsPoison] = poison;
-    }
-    return;
-  }
-  if (tid == 0 && fl != 0.0) *W.fail = 1;
-  __syncthreads();
-  finish_core(P, W, x, beta, x_new, beta_new, pm, dn, xn, gm, tid);
-  __syncthreads();
-  if (W.status[kWsHasCand] == 0.0) {
-    if (tid == 0) W.status[kWsJsel] = 2.0;   // nothing moved
-    return;
-  }
-  const bool accepted = accept_core(P, W, x, beta, x_new, beta_new, cost, tid, 256);
-  if (accepted && tid < NP) {
-    if (x_halo) x_halo[tid] = xn_halo[tid];
-    if (x_left) x_left[tid] = xn_left[tid];
-  }
-}
-
 }  // namespace
-
-size_t win_factor_lds_bytes() { return (size_t)(kCrRowsMax * LD + WB + 8 + 16 * 17) * sizeof(double); }
-size_t win_update_lds_bytes() { return (size_t)(2 * WB * LD + 2 * WR * LD) * sizeof(double); }
-size_t win_back_lds_bytes() { return (size_t)(WB * LD + 3 * WR * LD + 5 * 16 * 17) * sizeof(double); }
 
 void launch_win_init(const WinProblem& P, const WinBuf& W, const double* d_r, int mode, hipStream_t s) {
   BODYFIT_LAUNCH(k_win_init, dim3(1), dim3(1024), 0, s, P, W, d_r, mode);
@@ -1336,29 +650,6 @@ void launch_win_assemble(const WinProblem& P, const WinBuf& W, const double* d_H
                          hipStream_t s) {
   BODYFIT_LAUNCH(k_win_assemble, dim3(P.F), dim3(kAsmThreads), 0, s, P, W, d_Hpan, d_r, d_x, d_constant, first, d_x_left,
                      d_scale_halo);
-}
-void launch_cr_factor(const WinBuf& W, const int* d_elim, int n_elim, hipStream_t s) {
-  static DeviceOnce attr;
-  attr.run(current_device(), [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cr_factor), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)win_factor_lds_bytes());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cr_update), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)win_update_lds_bytes());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_cr_back), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)win_back_lds_bytes());
-  });
-  if (n_elim > 0)
-    BODYFIT_LAUNCH(k_cr_factor, dim3(2 * n_elim), dim3(kCrThreads), win_factor_lds_bytes(), s, d_elim, W.D, W.U, W.Rt, n_elim, W);
-}
-void launch_cr_update(const WinBuf& W, const int* d_surv, int n_surv, hipStream_t s) {
-  if (n_surv > 0) {
-    const int split = 4 * n_surv <= 256 ? 1 : 0;        // (the diagonal block in two workgroups where CUs are idle anyway)
-    BODYFIT_LAUNCH(k_cr_update, dim3((split ? 4 : 3) * n_surv), dim3(kCrThreads), win_update_lds_bytes(), s, d_surv, n_surv, split,
-                   W.D, W.Qt, W.Pt, W);
-  }
-}
-void launch_cr_back(const WinBuf& W, const int* d_elim, int n_elim, hipStream_t s) {
-  if (n_elim > 0) BODYFIT_LAUNCH(k_cr_back, dim3(n_elim), dim3(kCrThreads), win_back_lds_bytes(), s, d_elim, W.L, W.Xt, n_elim, W);
 }
 void launch_win_schur_part(const WinProblem& P, const WinBuf& W, hipStream_t s) {
   BODYFIT_LAUNCH(k_win_schur_part, dim3(P.F), dim3(128), 0, s, P, W);
@@ -1385,33 +676,4 @@ void launch_win_accept(const WinProblem& P, const WinBuf& W, const double* d_r_n
   BODYFIT_LAUNCH(k_win_accept, dim3(1), dim3(1024), 0, s, P, W, d_r_new, d_x, d_beta, d_x_new, d_beta_new, mode);
 }
 
-}  // namespace bodyfit
-
-namespace bodyfit {
-void launch_sum_ranks(const double* d_g, int N, int stride, int n, double* d_out, hipStream_t s) {
-  BODYFIT_LAUNCH(k_sum_ranks, dim3((n + 255) / 256), dim3(256), 0, s, d_g, N, stride, n, d_out);
-}
-void launch_replicate_ranks(double* d_g, int n, int N, hipStream_t s) {
-  BODYFIT_LAUNCH(k_replicate_ranks, dim3(std::min(64, (n + 255) / 256)), dim3(256), 0, s, d_g, n, N);
-}
-int iface_doubles(int n_extra) { return 4 * WB * WB + 2 * WR * WB + n_extra; }
-void launch_iface_pack(const WinBuf& W, int F, const double* d_extra, int n_extra, double* d_send, hipStream_t s) {
-  BODYFIT_LAUNCH(k_iface_pack, dim3(64), dim3(256), 0, s, W, F, d_extra, n_extra, d_send);
-}
-void launch_iface_unpack(const WinBuf& Wi, const double* d_g, int N, int n_extra, double* d_extra_sum, hipStream_t s) {
-  BODYFIT_LAUNCH(k_iface_unpack, dim3(64), dim3(256), 0, s, Wi, d_g, N, n_extra, d_extra_sum);
-}
-void launch_win_halo_step(const WinProblem& P, const double* d_Xi, const double* d_dsb, int node_right, const double* d_scale_right,
-                          const double* d_x_right, double* d_d_right, double* d_xn_right, int node_left,
-                          const double* d_scale_left, const double* d_x_left, double* d_xn_left, hipStream_t s) {
-  BODYFIT_LAUNCH(k_win_halo_step, dim3(2), dim3(128), 0, s, P, d_Xi, d_dsb, node_right, d_scale_right, d_x_right, d_d_right,
-                     d_xn_right, node_left, d_scale_left, d_x_left, d_xn_left);
-}
-void launch_win_fold_fail(const WinBuf& W, const WinBuf& Wi, hipStream_t s) { BODYFIT_LAUNCH(k_win_fold_fail, dim3(1), dim3(64), 0, s, W, Wi); }
-void launch_win_decide(const WinProblem& P, const WinBuf& W, double* d_x, double* d_beta, double* d_x_new, double* d_beta_new,
-                       const double* d_g, int N, double* d_x_halo, const double* d_xn_halo, double* d_x_left,
-                       const double* d_xn_left, hipStream_t s) {
-  BODYFIT_LAUNCH(k_win_decide, dim3(1), dim3(256), 0, s, P, W, d_x, d_beta, d_x_new, d_beta_new, d_g, N, d_x_halo, d_xn_halo,
-                     d_x_left, d_xn_left);
-}
 }  // namespace bodyfit

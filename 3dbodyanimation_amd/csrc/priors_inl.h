@@ -15,6 +15,7 @@
 // the waves through LDS (first minimum, as the sequential reference loop) and only the winner writes its rows.
 #pragma once
 #include "bodyfit_device.h"
+#include "device_util_inl.h"
 
 namespace bodyfit {
 
@@ -30,7 +31,7 @@ __device__ inline void temporal_rows(const PriorArgs& A, int f0, const double* _
   for (int i = threadIdx.x; i < kPriorTileF * T; i += 512) {
     const int f = f0 + i / T, c = i % T;
     if (f < A.n_pairs) {
-      const int src = (c < 3) ? (4 + c) : (c < 6 ? (1 + (c - 3)) : (7 + (c - 6)));
+      const int src = (c < 3) ? (4 + c) : (c < 6 ? (1 + (c - 3)) : (7 + (c - 6)));   // (inverse: device_util_inl.h temporal_row)
       const double v = A.lambda_t * (params[(size_t)f * npose + src] - params[(size_t)(f + 1) * npose + src]);
       A.r_temporal[(size_t)f * T + c] = v; pcost += 0.5 * v * v;
     }

@@ -83,6 +83,21 @@ def test_per_device_attribute_bookkeeping(tmp_path):
     assert res.returncode == 0 and "ok" in res.stdout, res.stdout
 
 
+def test_trust_region_rule_matches_the_checkers_statement(tmp_path):
+    """csrc/lm_rules.h — the one statement of Ceres' trust-region rule that the host loop and every device solver call — on a
+    fixed table of inputs, bit for bit against values computed from oracle/lm_dense.py's statement of the rule
+    (tests/cpp/lm_rules_test.cpp); compiled by g++, so it is also the proof that the header is plain C++."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "lm_rules_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(root, "tests", "cpp", "lm_rules_test.cpp"), "-o", exe])
+    res = subprocess.run([exe], capture_output=True, text=True)
+    assert res.returncode == 0 and "ok" in res.stdout, res.stdout
+
+
 def test_exchange_bound_of_the_sharded_solve(tmp_path):
     """bodyfit_set_exchange_timeout's mechanism (csrc/exchange_timeout.h) on the CPU: two ranks exchanging through blocking
     callbacks, one rank's transport fails — both are back within the bound (tests/cpp/exchange_timeout_test.cpp; the GPU suite

@@ -1,7 +1,7 @@
 // Diagnostic: where one k_cr_factor workgroup (the window LM's 80 x 80 block factorisation with 96 appended rows) spends its
 // cycles.  Includes the product's translation unit with -DBODYFIT_CR_STAMPS (wave 0 writes s_memtime per phase).
 // Build:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -DBODYFIT_CR_STAMPS -I3dbodyanimation_amd/csrc -o tools/ubench/cr_factor_phases tools/ubench/cr_factor_phases.hip
-#include "../../3dbodyanimation_amd/csrc/k_window_lm.hip"
+#include "../../3dbodyanimation_amd/csrc/k_window_cr.hip"
 
 #include <cstdio>
 #include <cstring>
