@@ -223,6 +223,14 @@ def load_library():
                                                   C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.bodyfit_closest_points_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.POINTER(PointSet), C.c_int, C.c_longlong,
                                                       C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_surface_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]
+    lib.bodyfit_surface_destroy.argtypes = [C.c_void_p]
+    lib.bodyfit_surface_destroy.restype = None
+    lib.bodyfit_closest_surface_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int, C.c_longlong,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.bodyfit_closest_surface_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int,
+                                                       C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
     lib.bodyfit_writeback_batch.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _dp]
     lib.bodyfit_evaluate_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_dp), _dp, C.POINTER(_dp)]
     _u8p = C.POINTER(C.c_uint8)
@@ -673,6 +681,58 @@ class ClosestPoints:
     def close(self):
         if getattr(self, "h", None):
             load_library().bodyfit_closest_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Surface:
+    """Closest point on the triangles of a posed mesh for every query point, and the gradient of the squared distances at the
+    fixed correspondence (bodyfit_surface_*, bodyfit_closest_surface_*, csrc/k_closest_surface.hip).  The handle holds one
+    topology (faces: int32 [n_faces, 3] with ids in [0, n_verts)) and the workspace of both calls; calls on one handle must be
+    ordered (one stream, or events)."""
+
+    def __init__(self, device: int, n_verts: int, faces):
+        f = np.asarray(faces)
+        if f.dtype.kind not in "iu":
+            raise TypeError("faces must be an integer array")
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"faces must be [n_faces, 3], got {f.shape}")
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        h = C.c_void_p()
+        _check(load_library().bodyfit_surface_create(int(device), int(n_verts), int(f.shape[0]),
+                                                     f.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(h)))
+        self.h = h
+        self.device = device
+        self.n_verts = int(n_verts)
+        self.n_faces = int(f.shape[0])
+
+    def closest_device(self, query: PointSet, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, n_query_total: int,
+                       d_dist2_ptr: int, d_index_ptr: int, d_bary_ptr: int, stream: int | None = None,
+                       prepare_vjp: bool = False):
+        """bodyfit_closest_surface_device: dist2 [N] f32, frame-local triangle index [N] int32 (-1: none) and barycentric
+        weights [N, 3] f32 of every query row, asynchronous on `stream`.  prepare_vjp: also group the queries by face for a
+        vjp_device call with this index (kept in the handle)."""
+        _check(load_library().bodyfit_closest_surface_device(self.h, C.byref(query), d_verts_ptr, int(verts_frame_stride),
+                                                             int(n_frames), int(n_query_total), d_dist2_ptr, d_index_ptr,
+                                                             d_bary_ptr, int(bool(prepare_vjp)), stream))
+
+    def vjp_device(self, query: PointSet, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, n_query_total: int,
+                   d_index_ptr: int, d_bary_ptr: int, d_grad_dist2_ptr: int, d_grad_query_ptr: int | None,
+                   d_grad_verts_ptr: int | None, stream: int | None = None):
+        """bodyfit_closest_surface_vjp_device: dL/dquery (layout of the query set) and dL/dverts (layout of the vertices; either
+        may be None) given dL/ddist2 [N] and the index and weights of closest_device, asynchronous on `stream`."""
+        _check(load_library().bodyfit_closest_surface_vjp_device(self.h, C.byref(query), d_verts_ptr, int(verts_frame_stride),
+                                                                 int(n_frames), int(n_query_total), d_index_ptr, d_bary_ptr,
+                                                                 d_grad_dist2_ptr, d_grad_query_ptr, d_grad_verts_ptr, stream))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().bodyfit_surface_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -21,6 +21,15 @@ obj.cost(r) is the Ceres cost of the problem (HuberLoss on the keypoint blocks, 
 
 closest_points is bodyfit_closest_points_device (k_closest.hip: brute force from LDS, no [F, N, V] intermediate); its backward is
 bodyfit_closest_points_vjp_device, with the correspondence held fixed, deterministic like the other gradients here.
+
+    dist2, index, bary = closest_surface(points, verts, faces, query_offset=offset)   # ... against its frame's TRIANGLES
+    term = SurfaceTerm(points, offset, faces)                                         # the scan -> surface cost
+    (obj.cost(obj(x, beta)) + w * term(layer(x, beta)[0])).backward()
+
+closest_surface is bodyfit_closest_surface_device (k_closest_surface.hip: prepared triangle records streamed through LDS, a
+conservative sphere cull, no [F, N, n_faces] intermediate): a point on the posed surface costs nothing wherever it falls between
+the vertices, which the point-to-point term cannot offer.  Its backward is bodyfit_closest_surface_vjp_device at the fixed
+(index, bary), which by the envelope theorem is the true gradient of the squared distance almost everywhere.
 """
 from __future__ import annotations
 
@@ -347,3 +356,146 @@ class PointCloudTerm(torch.nn.Module):
         if self.bidirectional:
             cost = cost + self._rho(*closest_points(verts, self.points, ref_offset=self.offset))
         return cost
+
+
+# ---- scan -> surface term -------------------------------------------------------------------------------------------------
+_surface_handles: dict[tuple, tuple] = {}   # (device, V, n_faces, content hash) -> (the faces' bytes, api.Surface); the last _SURFACE_CACHE in use
+_SURFACE_CACHE = 8
+
+
+def _host_faces(faces) -> np.ndarray:
+    """the checked int32 [n_faces, 3] host array of `faces` (a CUDA tensor is copied to the host: a synchronisation)"""
+    if isinstance(faces, torch.Tensor):
+        if faces.dtype != torch.int32:
+            raise TypeError("faces must be int32")
+        f = faces.detach().cpu().numpy()
+    else:
+        f = np.asarray(faces)
+        if f.dtype != np.int32:
+            raise TypeError("faces must be int32")
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces must be [n_faces, 3], got {tuple(f.shape)}")
+    return np.ascontiguousarray(f)
+
+
+def _surface_handle(device_index: int, n_verts: int, faces):
+    """The api.Surface of (device, topology).  An api.Surface is used as it is.  Anything else is keyed on its CONTENT (hashed on
+    every call and compared byte for byte on a hit, so an array changed in place is a new topology); the cache keeps the handles of the last _SURFACE_CACHE
+    topologies, an evicted handle is released when the last backward that holds it has run."""
+    if isinstance(faces, api.Surface):
+        if faces.device != device_index or faces.n_verts != n_verts:
+            raise ValueError(f"this Surface is for cuda:{faces.device} and {faces.n_verts} vertices, got cuda:{device_index} and {n_verts}")
+        return faces
+    f = _host_faces(faces)
+    raw = f.tobytes()
+    key = (device_index, int(n_verts), f.shape[0], hash(raw))
+    hit = _surface_handles.pop(key, None)
+    if hit is not None and hit[0] != raw:        # (two topologies under one hash: the kept one makes way)
+        hit = None
+    if hit is None:
+        if f.size and (int(f.min()) < 0 or int(f.max()) >= n_verts):
+            raise ValueError(f"faces holds an id outside [0, {n_verts})")
+        hit = (raw, api.Surface(device_index, n_verts, f))
+    _surface_handles[key] = hit                     # (most recently used last)
+    h = hit[1]
+    while len(_surface_handles) > _SURFACE_CACHE:
+        _surface_handles.pop(next(iter(_surface_handles)))
+    return h
+
+
+class _ClosestSurface(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, verts, faces, query_offset):
+        q, qs, F, nq = _point_set("points", points, query_offset)
+        if not isinstance(verts, torch.Tensor):
+            raise TypeError("verts must be a torch tensor")
+        if verts.dtype != torch.float32:
+            raise TypeError("verts must be float32")
+        if not verts.is_cuda:
+            raise ValueError("verts must be on the GPU")
+        if verts.ndim != 3 or verts.shape[2] != 3:
+            raise ValueError(f"verts must be [F, V, 3], got {tuple(verts.shape)}")
+        v, vs, Fv, _ = _point_set("verts", verts, None)
+        if F != Fv:
+            raise ValueError(f"points has {F} frames, verts has {Fv}")
+        if v.device != q.device:
+            raise ValueError("points and verts must be on the same GPU")
+        handle = _surface_handle(q.device.index, v.shape[1], faces)
+        dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
+        index = torch.empty(nq, dtype=torch.int32, device=q.device)
+        bary = torch.empty((nq, 3), dtype=torch.float32, device=q.device)
+        if nq > 0:
+            handle.closest_device(qs, v.data_ptr(), vs.frame_stride, F, nq, dist2.data_ptr(), index.data_ptr(), bary.data_ptr(),
+                                  _stream(), prepare_vjp=ctx.needs_input_grad[1])
+        ctx.sets = (qs, vs, F, nq, handle)
+        ctx.save_for_backward(q, v, index, bary)
+        ctx.mark_non_differentiable(index, bary)
+        return dist2, index, bary
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_dist2, _g_index, _g_bary):
+        q, v, index, bary = ctx.saved_tensors
+        qs, vs, F, nq, handle = ctx.sets
+        want_q, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gq = _grad_like(q, qs) if want_q else None
+        gv = _grad_like(v, vs) if want_v else None
+        if g_dist2 is None or nq == 0:
+            for g in (gq, gv):
+                if g is not None:
+                    g.zero_()
+        else:
+            g = g_dist2.to(torch.float32).contiguous()
+            handle.vjp_device(qs, v.data_ptr(), vs.frame_stride, F, nq, index.data_ptr(), bary.data_ptr(), g.data_ptr(),
+                              gq.data_ptr() if gq is not None else None, gv.data_ptr() if gv is not None else None, _stream())
+        return gq, gv, None, None
+
+
+def closest_surface(points: torch.Tensor, verts: torch.Tensor, faces, query_offset: torch.Tensor | None = None):
+    """For every point the closest point on the triangles (verts[f][faces[t]]) of its frame: (dist2 [N] f32, index [N] int32,
+    the frame-local triangle, bary [N, 3] f32, the barycentric weights of the closest point), packed in frame order; -1, +inf
+    and zeros where no finite candidate exists (no faces, a NaN point).
+
+    points: f32 on the GPU, [F, n, 3], or [N, 3] with an int32 query_offset [F + 1] (the conventions of closest_points).  verts:
+    [F, V, 3] f32 on the same GPU (a view whose frames are farther apart than 3 V floats is used without a copy).  faces: int32
+    [n_faces, 3] with ids in [0, V): a HOST array or CPU tensor (its content is hashed on every call to find the kept handle of
+    the (device, topology); a CUDA tensor is accepted but copied to the host first, which synchronises), or an api.Surface, which
+    skips both (SurfaceTerm does that).  dist2 is differentiable with respect to points and verts at the fixed (index, bary);
+    index and bary carry no gradient.  Runs on torch.cuda.current_stream(); with host faces or an api.Surface there is no host
+    synchronisation (bodyfit_closest_surface_device and its _vjp_device, k_closest_surface.hip).  Calls on one topology share a workspace: interleaving them on several streams at once needs the
+    caller's own ordering."""
+    return _ClosestSurface.apply(points, verts, faces, query_offset)
+
+
+class SurfaceTerm(torch.nn.Module):
+    """The scan -> surface data term of a sequence: sum over the target points of rho(squared distance to the closest point on
+    the frame's triangles).
+
+    points: [N, 3] f32 on the GPU with offset, int32 [F + 1], or [F, n, 3] with offset None.  faces: int32 [n_faces, 3].
+    trunc = tau: rho(s) = min(s, tau^2); None: rho(s) = s.  term(verts), verts [F, V, 3] f32 (SMPLLayer's first output), returns
+    the f64 cost; a point without a counterpart (index -1) costs nothing."""
+
+    def __init__(self, points: torch.Tensor, offset: torch.Tensor | None, faces, trunc: float | None = None):
+        super().__init__()
+        _point_set("points", points, offset)   # the checks
+        if trunc is not None and not trunc > 0.0:
+            raise ValueError("trunc must be positive")
+        f = _host_faces(faces)
+        self.register_buffer("points", points.detach())
+        self.register_buffer("offset", offset.detach() if offset is not None else None)
+        self.faces = f.copy()                    # the term's own topology: later changes to the caller's array do not reach it
+        self.trunc = None if trunc is None else float(trunc)
+        self._handles: dict[tuple, object] = {}  # (device, V) -> api.Surface, owned by the term
+
+    def forward(self, verts: torch.Tensor) -> torch.Tensor:
+        faces = self.faces
+        if isinstance(verts, torch.Tensor) and verts.is_cuda and verts.ndim == 3:
+            key = (verts.device.index, verts.shape[1])
+            faces = self._handles.get(key)
+            if faces is None:
+                faces = self._handles[key] = _surface_handle(key[0], key[1], self.faces)
+        dist2, index, _ = closest_surface(self.points, verts, faces, query_offset=self.offset)
+        s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))
+        if self.trunc is not None:
+            s = torch.clamp(s, max=self.trunc * self.trunc)
+        return s.double().sum()

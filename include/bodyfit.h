@@ -359,6 +359,81 @@ int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset
                                       int n_frames, long long n_query_total, long long n_ref_total, const int32_t* d_index,
                                       const float* d_grad_dist2, float* d_grad_query, float* d_grad_ref, void* stream);
 
+/* ---- closest point on the mesh SURFACE (the scan -> surface data term: a point on the posed surface costs nothing) ----------
+ * A bodyfit_surface holds one topology on one device: the faces, the vertex -> (face, corner) CSR of the backward, and the
+ * workspace of both calls (O(N + F n_faces): prepared triangle records, the splits' partial minima, the groupings of the last
+ * four prepare_vjp searches, per-face gradient sums).  faces: host int32 [n_faces][3]; an id outside [0, n_verts) is
+ * BODYFIT_ERR_INVALID; n_faces = 0 is accepted.  Degenerate faces (zero area, a repeated id, collinear corners) are legal: the
+ * closest point is that of the segment or point the face collapses to.                                                        */
+typedef struct bodyfit_surface bodyfit_surface;
+int bodyfit_surface_create(int device, int n_verts, int n_faces, const int32_t* faces, bodyfit_surface** out);
+void bodyfit_surface_destroy(bodyfit_surface* s);
+/* For every query point p of frame f (query: a bodyfit_pointset of either kind), over the triangles
+ * (verts[f][faces[t][0..2]]) of that frame (d_verts [F][n_verts][3] f32, verts_frame_stride floats between frames, >= 3 n_verts:
+ * bodyfit_device_views.cloud is used in place): d_index the frame-local triangle, d_bary [N][3] the barycentric weights of the
+ * closest point, d_dist2 the squared distance, packed in frame order like bodyfit_closest_points_device's outputs.
+ * CONTRACT.  With c^ = sum_i b_i v_faces[index][i] and d^ = |p - c^| evaluated exactly from the f32 inputs, d* the exact minimum
+ * distance from p to any triangle of the frame, h the longest edge of the returned triangle, u = 2^-24 and k = 32:
+ *   b_i >= 0 and b_0 + b_1 + b_2 = 1 exactly (the weights are multiples of 2^-23);
+ *   optimality   d^ <= d* + k u (d* + h);        consistency   |sqrt(d_dist2) - d^| <= k u (d^ + h).
+ * The bound is on distances, never on which triangle wins: shared edges and vertices tie exactly.  Among equal COMPUTED
+ * distances the lowest triangle index wins.
+ * Derivation of k (k_closest_surface.hip).  A triangle T is evaluated in the orthonormal frame (u, w) of its longest edge AB,
+ * prepared in f64 and rounded once, so a thin face loses nothing.  Write e = u (d_T + h_T) with d_T the exact distance of p to T
+ * and h_T its longest edge; every quantity below is bounded by |p - A| <= d_T + h_T, and errors are absolute lengths.
+ *  (1) what T's evaluation returns against T's exact closest point, E_T:
+ *      X = ap . u and Y = ap . w: ap = p - A one rounding (|ap| u), a three-term dot three (3 |ap| u), the rounded unit vector
+ *      one (|ap| u): 5 e per axis, 7.1 e for the in-plane point (x sqrt 2);
+ *      the stored L, cx, t, one rounding each of lengths <= h_T: the 2-D triangle is off by at most 2 e;
+ *      the projection onto an edge S + tau D: the dot (two terms of size |P - S| |D|) 2, the stored 1/|D|^2 1, the product 1,
+ *      the point S + tau D 2: tau |D| is off by 6 u |P - S| <= 6 e;
+ *      choosing among the candidates by their computed in-plane distances, each a sum of two squares of differences known to
+ *      1.5 e: a wrong choice costs at most 3 e;
+ *      the frame: u . w and |u|, |w| are off by u each, which tilts the 2-D picture by at most 2 e.      E_T <= 20.1 e.
+ *  (2) the weights from (qx, qy): two divisions and one fused product (3 roundings of numbers <= 1, each moving c^ by u h_T),
+ *      two roundings to 2^-23 (2^-24 each on a weight, the third weight takes both: 3 u h_T): 6 e.
+ *  (3) dist2 against |p - (A + qx u + qy w)|^2: two fused steps per component on terms <= 3 (d_T + h_T), 6 e per component,
+ *      10.4 e for the vector (x sqrt 3); the sum of squares and the root 2 e; u L against B - A and w t against C's offset 2 e:
+ *      with (2), consistency 20.4 e, stated as k = 32.
+ *  Optimality: the winner W has the smallest computed distance, so its point is bounded through the exactly closest triangle
+ *  T*: d^_W <= d* + E_T* + 6 e_W.  With W = T* that is 26.1 e, stated as k = 32.  With W != T* the evaluation error of T* scales
+ *  with ITS longest edge, so what holds without condition is the bound with h = max(h_W, h_T*); the form above, in the returned
+ *  triangle's h alone, holds whenever h_T* <= 1.29 h_W (20.1 of the units ride on h_T*, 32 - 6 = 26 are available), as between
+ *  the neighbouring faces of a mesh, where such ties occur.  No f32 evaluation can promise more: a point d* from a large face
+ *  and d* + delta from a small one, delta below the rounding of p - A at the large face's size, cannot be told apart.  The
+ *  tests assert the stricter form, in the returned triangle's h, for every query of their face soups.
+ * A conservative cull skips a triangle when the computed squared distance to the midpoint of AB exceeds (s + R)^2, with
+ * s = sqrt(best) (1 + 2^-12) and R = (1 + 2^-12) x the radius of the sphere about that midpoint (R >= L / 2).  Its margin in
+ * distance is at least 2^-12 (sqrt(best) + R) >= 2^-13 L = 2048 u L.  Against it: the midpoint distance in the expanded form
+ * |ap|^2 - L X + L^2 / 4 carries at most 6 u (|ap| + L)^2; far away (|ap| > 4 L) that is a relative 10 u, nothing beside
+ * 2^-12; nearer, 150 u L^2, which over twice the distance (>= R >= L / 2) is 150 u L; and the pair's own evaluation error,
+ * k u (d + h) with d <= 5 L and h = L, is 192 u L: 342 u L < 2048 u L.  So a culled triangle's COMPUTED distance is above the
+ * running best; it could neither win nor tie, and the cull never changes an output bit.
+ * Deterministic: bit-identical from run to run, whatever the split of the face range and whatever n_frames (a frame's outputs
+ * depend on that frame only).
+ * A NaN / Inf query, or a triangle with a non-finite corner, never wins; a query without a finite candidate (also n_faces = 0)
+ * gets d_index = -1, d_dist2 = +inf, d_bary = 0.  prepare_vjp = 1 also groups the queries by the face they chose and keeps
+ * that in the handle, as for bodyfit_closest_points_device.  Asynchronous on `stream`; a call that has to grow the handle's
+ * workspace synchronises the device once; calls on one handle share the workspace: order them.  n_frames == 0 or no query
+ * rows: a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / set / outputs, negative counts, a stride below 3 n_verts.    */
+int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
+                                   long long verts_frame_stride, int n_frames, long long n_query_total, float* d_dist2,
+                                   int32_t* d_index, float* d_bary, int prepare_vjp, void* stream);
+/* Reverse-mode gradient at the fixed correspondence (d_index and d_bary held; by the envelope theorem the true gradient of the
+ * squared distance almost everywhere, since the weights minimise): with c^_i = sum_a b_ia v_faces[index_i][a],
+ *   d_grad_query[i] = 2 g_i (p_i - c^_i),     d_grad_verts[f][v] = sum over (i, a) with faces[index_i][a] = v of -2 g_i b_ia (p_i - c^_i),
+ * d_grad_query in the layout of the query set, d_grad_verts in that of d_verts (every vertex row of every frame is written,
+ * zeros where nothing maps; the padding behind a frame is left untouched).  Either output may be NULL.  d_index = -1 or out of
+ * range contributes nothing.  f32; p - c^ is formed as (p - v0) - b1 (v1 - v0) - b2 (v2 - v0).  Deterministic: no float
+ * atomics; per face the queries that chose it in ascending order (more than 64: 64 interleaved ascending partial sums, then a
+ * fixed tree), then per vertex its incident (face, corner) sums in ascending order.  The grouping is taken from the handle
+ * when d_index is the output of one of its last four prepare_vjp searches over the same set and counts, else built inside this
+ * call, with the same result bit for bit.  Asynchronous and ordered like bodyfit_closest_surface_device.                     */
+int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
+                                       long long verts_frame_stride, int n_frames, long long n_query_total, const int32_t* d_index,
+                                       const float* d_bary, const float* d_grad_dist2, float* d_grad_query, float* d_grad_verts,
+                                       void* stream);
+
 /* The post-solve write-back of a whole solve on the device: for every frame
  *   r[0] <- R(rootAA) r[0]  (left-multiplied, so it compounds over repeated solves),  p <- rootT,
  *   r[j] <- R(jointAA[j]),  Avatar::update()  (the Sim3 scale is dropped),
