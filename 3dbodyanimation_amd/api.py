@@ -228,6 +228,9 @@ def load_library():
     lib.bodyfit_surface_destroy.restype = None
     lib.bodyfit_closest_surface_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int, C.c_longlong,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.bodyfit_closest_surface_oriented_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_float, C.c_void_p,
+                                                            C.c_longlong, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_int, C.c_void_p]
     lib.bodyfit_closest_surface_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int,
                                                        C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
@@ -720,6 +723,18 @@ class Surface:
         _check(load_library().bodyfit_closest_surface_device(self.h, C.byref(query), d_verts_ptr, int(verts_frame_stride),
                                                              int(n_frames), int(n_query_total), d_dist2_ptr, d_index_ptr,
                                                              d_bary_ptr, int(bool(prepare_vjp)), stream))
+
+    def closest_oriented_device(self, query: PointSet, d_normals_ptr: int, min_cos: float, d_verts_ptr: int,
+                                verts_frame_stride: int, n_frames: int, n_query_total: int, d_dist2_ptr: int, d_index_ptr: int,
+                                d_bary_ptr: int, stream: int | None = None, prepare_vjp: bool = False):
+        """bodyfit_closest_surface_oriented_device: closest_device over the triangles whose face normal n (orientation of
+        `faces`) has n . m >= min_cos, m the direction of the query row (d_normals_ptr: [N, 3] f32, packed like dist2 whatever
+        the layout of `query`).  A row without a compatible triangle gets -1, +inf, 0.  vjp_device takes the result as it takes
+        closest_device's."""
+        _check(load_library().bodyfit_closest_surface_oriented_device(self.h, C.byref(query), d_normals_ptr, float(min_cos),
+                                                                      d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                                      int(n_query_total), d_dist2_ptr, d_index_ptr, d_bary_ptr,
+                                                                      int(bool(prepare_vjp)), stream))
 
     def vjp_device(self, query: PointSet, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, n_query_total: int,
                    d_index_ptr: int, d_bary_ptr: int, d_grad_dist2_ptr: int, d_grad_query_ptr: int | None,

@@ -1,6 +1,8 @@
 // k_closest_surface.hip — closest point on a frame's TRIANGLES for every query point, and its reverse-mode gradient
 // (bodyfit_surface_*, bodyfit_closest_surface_device, bodyfit_closest_surface_vjp_device; declared in include/bodyfit.h).  The
 // point-to-surface scan term: a scan point that lies on the posed surface costs nothing, wherever it falls between the vertices.
+// bodyfit_closest_surface_oriented_device is the same search over the triangles whose face normal agrees with a direction the
+// query carries (k_cs_search<true>: the gate is described at the kernel).
 //
 // Prepared record (k_cs_prepare, once per call, one thread per (frame, face), in f64 from the f32 corners, rounded once to
 // f32; 16 floats):  the corners are rotated so that A -> B is the LONGEST edge (the lowest rotation among equals), C the third;
@@ -72,6 +74,8 @@ struct SurfArgs {
   float4* rec;              // [F][n_faces][4]
   float* dist2; int* index; float* bary;
   float* part_d; int* part_i;
+  const float* qn;          // oriented search: the queries' directions, packed [nq_total][3] in the row order of dist2
+  float min_cos;            // oriented search: a triangle is a candidate iff (u x w) . m >= min_cos
 };
 
 __global__ __launch_bounds__(256) void k_cs_prepare(const SurfArgs a) {
@@ -184,6 +188,11 @@ __device__ __forceinline__ float eval_tri(float ax, float ay, float az, float X,
   return fmaf(rz, rz, fmaf(ry, ry, rx * rx));
 }
 
+// kOriented: the normal-compatible search (bodyfit_closest_surface_oriented_device).  The face normal is n = u x w of the record
+// (the corner rotation of k_cs_prepare is cyclic, so (B - A) x (C - A) = L t (u x w) keeps the orientation of `faces`); a record
+// without a height (t = 0) has no normal and is never a candidate.  The gate sits between the cull and the evaluation and only
+// removes candidates, so the cull argument stands; everything written with `if constexpr` is absent from the other instantiation.
+template <bool kOriented>
 __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
   __shared__ float4 s_rec[4 * kSTileT];
   __shared__ float s_d[kSWaves][kSTileQ];
@@ -208,6 +217,7 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
   const int q0 = tile * kSTileQ;
   if (q0 >= fq.count) return;
   float px[kSQ], py[kSQ], pz[kSQ], best[kSQ], bs[kSQ];
+  [[maybe_unused]] float mx[kSQ], my[kSQ], mz[kSQ];
   int bi[kSQ];
 #pragma unroll
   for (int k = 0; k < kSQ; ++k) {
@@ -215,6 +225,10 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
     const bool ok = qi < fq.count;
     const float* p = a.q.xyz + fq.first + 3 * (size_t)(ok ? qi : q0);
     px[k] = p[0]; py[k] = p[1]; pz[k] = p[2];
+    if constexpr (kOriented) {
+      const float* m = a.qn + 3 * (size_t)(fq.row0 + (ok ? qi : q0));
+      mx[k] = m[0]; my[k] = m[1]; mz[k] = m[2];
+    }
     best[k] = std::numeric_limits<float>::infinity(); bs[k] = best[k]; bi[k] = -1;
   }
   int c0 = 0, c1 = a.n_faces;
@@ -235,6 +249,13 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
       const int ci = t0 + j;
       const float L = r0.w, R = r3.x;
       const float Lq = 0.25f * L * L;
+      [[maybe_unused]] float nx, ny, nz;
+      if constexpr (kOriented) {   // (the record is the same in every lane: so is this branch)
+        if (!(r2.w > 0.f)) continue;
+        nx = fmaf(r1.y, r2.z, -(r1.z * r2.y));
+        ny = fmaf(r1.z, r2.x, -(r1.x * r2.z));
+        nz = fmaf(r1.x, r2.y, -(r1.y * r2.x));
+      }
 #pragma unroll
       for (int k = 0; k < kSQ; ++k) {
         const float ax = px[k] - r0.x, ay = py[k] - r0.y, az = pz[k] - r0.z;
@@ -243,6 +264,9 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
         const float dc2 = fmaf(-L, X, ap2 + Lq);
         const float reach = bs[k] + R;
         if (dc2 <= reach * reach) {   // (false for a NaN on either side: a non-finite query or face is never evaluated)
+          if constexpr (kOriented) {   // (false for a NaN in m or min_cos: that query has no candidate)
+            if (!(fmaf(nz, mz[k], fmaf(ny, my[k], nx * mx[k])) >= a.min_cos)) continue;
+          }
           float qx, qy;
           const float d = eval_tri(ax, ay, az, X, r1, r2, r3, L, &qx, &qy);
           if (d < best[k]) {
@@ -536,13 +560,19 @@ void bodyfit_surface_destroy(bodyfit_surface* s) {
   delete s;
 }
 
-int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
-                                   long long verts_frame_stride, int n_frames, long long n_query_total, float* d_dist2,
-                                   int32_t* d_index, float* d_bary, int prepare_vjp, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// both searches: `oriented` selects the instantiation of k_cs_search, nothing else differs
+int closest_surface_call(const char* fn, bool oriented, bodyfit_surface* s, const bodyfit_pointset* query,
+                         const float* d_query_normals, float min_cos, const float* d_verts, long long verts_frame_stride,
+                         int n_frames, long long n_query_total, float* d_dist2, int32_t* d_index, float* d_bary, int prepare_vjp,
+                         void* stream) {
   using namespace bodyfit;
-  const char* fn = "bodyfit_closest_surface_device";
   if (int rc = check_surface_call(fn, s, query, d_verts, verts_frame_stride, n_frames, &n_query_total)) return rc;
   if (!d_dist2 || !d_index || !d_bary) return invalid(fn, "d_dist2 / d_index / d_bary is NULL");
+  if (oriented && n_frames > 0 && n_query_total > 0 && !d_query_normals) return invalid(fn, "d_query_normals is NULL");
   if (n_frames == 0 || n_query_total == 0) return BODYFIT_OK;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -553,6 +583,7 @@ int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* q
   a.verts = d_verts; a.vstride = verts_frame_stride; a.faces = s->d_faces; a.n_faces = s->n_faces;
   a.F = n_frames; a.nq_total = n_query_total;
   a.dist2 = d_dist2; a.index = d_index; a.bary = d_bary;
+  a.qn = d_query_normals; a.min_cos = min_cos;
   const long long tiles = query->d_offset ? n_query_total / kSTileQ + n_frames
                                           : (long long)n_frames * ((query->n_per_frame + kSTileQ - 1) / kSTileQ);
   if (tiles >= (1LL << 31)) return invalid(fn, "too many query tiles");
@@ -575,7 +606,8 @@ int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* q
     a.part_i = reinterpret_cast<int*>(s->ws + part);
   }
   if (n_rows > 0) BODYFIT_LAUNCH(k_cs_prepare, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, a);
-  BODYFIT_LAUNCH(k_cs_search, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kSWaves), 0, st, a);
+  if (oriented) BODYFIT_LAUNCH(k_cs_search<true>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kSWaves), 0, st, a);
+  else BODYFIT_LAUNCH(k_cs_search<false>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kSWaves), 0, st, a);
   BODYFIT_LAUNCH(k_cs_finish, dim3((unsigned)((n_query_total + 255) / 256)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
   if (group) {   // (behind the fold on the stream: the scratch may lie over the partial minima)
@@ -584,6 +616,25 @@ int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* q
     if (int rc = build_grouping(s, query, &fr, n_frames, n_query_total, n_rows, d_index, true, st, &g)) return rc;
   }
   return BODYFIT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
+                                   long long verts_frame_stride, int n_frames, long long n_query_total, float* d_dist2,
+                                   int32_t* d_index, float* d_bary, int prepare_vjp, void* stream) {
+  return closest_surface_call("bodyfit_closest_surface_device", false, s, query, nullptr, 0.f, d_verts, verts_frame_stride, n_frames,
+                              n_query_total, d_dist2, d_index, d_bary, prepare_vjp, stream);
+}
+
+int bodyfit_closest_surface_oriented_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_query_normals,
+                                            float min_cos, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                            long long n_query_total, float* d_dist2, int32_t* d_index, float* d_bary,
+                                            int prepare_vjp, void* stream) {
+  return closest_surface_call("bodyfit_closest_surface_oriented_device", true, s, query, d_query_normals, min_cos, d_verts,
+                              verts_frame_stride, n_frames, n_query_total, d_dist2, d_index, d_bary, prepare_vjp, stream);
 }
 
 int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,

@@ -30,6 +30,13 @@ closest_surface is bodyfit_closest_surface_device (k_closest_surface.hip: prepar
 conservative sphere cull, no [F, N, n_faces] intermediate): a point on the posed surface costs nothing wherever it falls between
 the vertices, which the point-to-point term cannot offer.  Its backward is bodyfit_closest_surface_vjp_device at the fixed
 (index, bary), which by the envelope theorem is the true gradient of the squared distance almost everywhere.
+
+    dist2, index, bary = closest_surface(points, verts, faces, query_offset=offset, point_normals=normals, min_cos=0.5)
+    term = SurfaceTerm(points, offset, faces, normals=normals, min_cos=0.5)          # normal-compatible correspondences
+
+With point_normals (the scan's normals, or for a depth map the directions towards the sensor) a point may only match a triangle
+whose face normal n, in the orientation of faces, has n . m >= min_cos (bodyfit_closest_surface_oriented_device): the inside
+of the arm no longer matches the torso because the torso is nearer.  The gate is piecewise constant, so the backward is the same.
 """
 from __future__ import annotations
 
@@ -405,7 +412,7 @@ def _surface_handle(device_index: int, n_verts: int, faces):
 
 class _ClosestSurface(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points, verts, faces, query_offset):
+    def forward(ctx, points, verts, faces, query_offset, point_normals, min_cos):
         q, qs, F, nq = _point_set("points", points, query_offset)
         if not isinstance(verts, torch.Tensor):
             raise TypeError("verts must be a torch tensor")
@@ -424,7 +431,12 @@ class _ClosestSurface(torch.autograd.Function):
         dist2 = torch.empty(nq, dtype=torch.float32, device=q.device)
         index = torch.empty(nq, dtype=torch.int32, device=q.device)
         bary = torch.empty((nq, 3), dtype=torch.float32, device=q.device)
-        if nq > 0:
+        if point_normals is not None:
+            m = _packed_normals(point_normals, points)
+            if nq > 0:
+                handle.closest_oriented_device(qs, m.data_ptr(), min_cos, v.data_ptr(), vs.frame_stride, F, nq, dist2.data_ptr(),
+                                               index.data_ptr(), bary.data_ptr(), _stream(), prepare_vjp=ctx.needs_input_grad[1])
+        elif nq > 0:
             handle.closest_device(qs, v.data_ptr(), vs.frame_stride, F, nq, dist2.data_ptr(), index.data_ptr(), bary.data_ptr(),
                                   _stream(), prepare_vjp=ctx.needs_input_grad[1])
         ctx.sets = (qs, vs, F, nq, handle)
@@ -448,10 +460,28 @@ class _ClosestSurface(torch.autograd.Function):
             g = g_dist2.to(torch.float32).contiguous()
             handle.vjp_device(qs, v.data_ptr(), vs.frame_stride, F, nq, index.data_ptr(), bary.data_ptr(), g.data_ptr(),
                               gq.data_ptr() if gq is not None else None, gv.data_ptr() if gv is not None else None, _stream())
-        return gq, gv, None, None
+        return gq, gv, None, None, None, None
 
 
-def closest_surface(points: torch.Tensor, verts: torch.Tensor, faces, query_offset: torch.Tensor | None = None):
+def _packed_normals(normals, points) -> torch.Tensor:
+    """the checked directions of `points` as one packed [N, 3] f32 array in the row order of dist2"""
+    if not isinstance(normals, torch.Tensor):
+        raise TypeError("point_normals must be a torch tensor")
+    if normals.dtype != torch.float32:
+        raise TypeError("point_normals must be float32")
+    if not isinstance(points, torch.Tensor):
+        raise TypeError("points must be a torch tensor")
+    if normals.device != points.device:
+        raise ValueError("point_normals must be on the GPU of points")
+    if normals.shape != points.shape:
+        raise ValueError(f"point_normals must have the shape of points, {tuple(points.shape)}, got {tuple(normals.shape)}")
+    if normals.requires_grad:
+        raise ValueError("point_normals carries no gradient (the gate is piecewise constant): pass point_normals.detach()")
+    return normals.contiguous()
+
+
+def closest_surface(points: torch.Tensor, verts: torch.Tensor, faces, query_offset: torch.Tensor | None = None,
+                    point_normals: torch.Tensor | None = None, min_cos: float = 0.0):
     """For every point the closest point on the triangles (verts[f][faces[t]]) of its frame: (dist2 [N] f32, index [N] int32,
     the frame-local triangle, bary [N, 3] f32, the barycentric weights of the closest point), packed in frame order; -1, +inf
     and zeros where no finite candidate exists (no faces, a NaN point).
@@ -463,8 +493,17 @@ def closest_surface(points: torch.Tensor, verts: torch.Tensor, faces, query_offs
     skips both (SurfaceTerm does that).  dist2 is differentiable with respect to points and verts at the fixed (index, bary);
     index and bary carry no gradient.  Runs on torch.cuda.current_stream(); with host faces or an api.Surface there is no host
     synchronisation (bodyfit_closest_surface_device and its _vjp_device, k_closest_surface.hip).  Calls on one topology share a workspace: interleaving them on several streams at once needs the
-    caller's own ordering."""
-    return _ClosestSurface.apply(points, verts, faces, query_offset)
+    caller's own ordering.
+
+    point_normals: None (the search by distance alone), or a direction per point, f32 on the same GPU in the shape of points
+    ([N, 3] with an offset, [F, n, 3] without; made contiguous).  A point may then only match a triangle with an area whose face
+    normal n, in the orientation of faces, has n . m >= min_cos (a Python float); a point without such a triangle gets -1, +inf
+    and zeros (bodyfit_closest_surface_oriented_device).  The directions are used as given (pass unit vectors) and carry no
+    gradient: a point_normals that requires grad is a ValueError."""
+    if point_normals is not None:
+        _packed_normals(point_normals, points)   # (the checks, before autograd sees the tensor)
+        min_cos = float(min_cos)
+    return _ClosestSurface.apply(points, verts, faces, query_offset, point_normals, min_cos)
 
 
 class SurfaceTerm(torch.nn.Module):
@@ -472,18 +511,25 @@ class SurfaceTerm(torch.nn.Module):
     the frame's triangles).
 
     points: [N, 3] f32 on the GPU with offset, int32 [F + 1], or [F, n, 3] with offset None.  faces: int32 [n_faces, 3].
-    trunc = tau: rho(s) = min(s, tau^2); None: rho(s) = s.  term(verts), verts [F, V, 3] f32 (SMPLLayer's first output), returns
-    the f64 cost; a point without a counterpart (index -1) costs nothing."""
+    trunc = tau: rho(s) = min(s, tau^2); None: rho(s) = s.  normals: None, or a direction per point in the shape of points, with
+    min_cos the point_normals / min_cos of closest_surface: only normal-compatible triangles are matched.  term(verts), verts
+    [F, V, 3] f32 (SMPLLayer's first output), returns the f64 cost; a point without a counterpart (index -1: no faces, or no
+    compatible triangle) costs nothing."""
 
-    def __init__(self, points: torch.Tensor, offset: torch.Tensor | None, faces, trunc: float | None = None):
+    def __init__(self, points: torch.Tensor, offset: torch.Tensor | None, faces, trunc: float | None = None,
+                 normals: torch.Tensor | None = None, min_cos: float = 0.0):
         super().__init__()
         _point_set("points", points, offset)   # the checks
+        if normals is not None:
+            _packed_normals(normals, points)
         if trunc is not None and not trunc > 0.0:
             raise ValueError("trunc must be positive")
         f = _host_faces(faces)
         self.register_buffer("points", points.detach())
         self.register_buffer("offset", offset.detach() if offset is not None else None)
         self.faces = f.copy()                    # the term's own topology: later changes to the caller's array do not reach it
+        self.register_buffer("normals", normals.detach().contiguous() if normals is not None else None)
+        self.min_cos = float(min_cos)
         self.trunc = None if trunc is None else float(trunc)
         self._handles: dict[tuple, object] = {}  # (device, V) -> api.Surface, owned by the term
 
@@ -494,7 +540,8 @@ class SurfaceTerm(torch.nn.Module):
             faces = self._handles.get(key)
             if faces is None:
                 faces = self._handles[key] = _surface_handle(key[0], key[1], self.faces)
-        dist2, index, _ = closest_surface(self.points, verts, faces, query_offset=self.offset)
+        dist2, index, _ = closest_surface(self.points, verts, faces, query_offset=self.offset, point_normals=self.normals,
+                                          min_cos=self.min_cos)
         s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))
         if self.trunc is not None:
             s = torch.clamp(s, max=self.trunc * self.trunc)

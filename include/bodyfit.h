@@ -419,6 +419,40 @@ void bodyfit_surface_destroy(bodyfit_surface* s);
 int bodyfit_closest_surface_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
                                    long long verts_frame_stride, int n_frames, long long n_query_total, float* d_dist2,
                                    int32_t* d_index, float* d_bary, int prepare_vjp, void* stream);
+/* The ORIENTED search: bodyfit_closest_surface_device over the normal-compatible triangles only.  Query row i carries a
+ * direction m_i (d_query_normals: [N][3] f32, packed in frame order, row-aligned with d_dist2 whatever the layout of the query
+ * set; the scan's own normal, or for a depth map the direction towards the sensor).  A triangle is a candidate for the row iff
+ * it has an area and its face normal n, in the orientation of `faces` ((v1 - v0) x (v2 - v0) normalised), has n . m_i >= min_cos.
+ * m is used as given: the caller passes unit vectors; a zero vector has n . m = 0.  Among the candidates everything is as above:
+ * the same evaluation, cull, tie-break, outputs and conventions; a row without a candidate gets -1, +inf, 0.  The gate is
+ * piecewise constant in the vertices, so the gradient at the fixed (index, bary) is unchanged: the backward is
+ * bodyfit_closest_surface_vjp_device on the returned arrays, and a grouping prepared here (prepare_vjp) is found by it exactly as
+ * one of the unoriented search.  A NaN in m_i: row i has no candidate; a NaN min_cos: no row has.
+ * CONTRACT.  With u = 2^-24, k_n = 16 and tau_i = k_n u |m_i|, let n_t be the exact unit normal of the f32 corners of face t,
+ * "with area" the rule of the prepared record (height over the longest edge L above 2^-40 L and above 1e-30), and
+ *   strict_i = {t with area : n_t . m_i >= min_cos + tau_i},      loose_i = {t with area : n_t . m_i >= min_cos - tau_i}.
+ *   (1) the returned triangle is in loose_i, or d_index = -1;
+ *   (2) if strict_i is not empty, d_index != -1 and d^ <= d*_strict + k u (d*_strict + h), k = 32, with d^ and h as above and
+ *       d*_strict the exact minimum distance from p_i to the triangles of strict_i;
+ *   (3) if loose_i is empty, d_index = -1;
+ *   (4) the properties of b_i and the consistency bound hold as above;
+ *   (5) deterministic and frame-independent as above: a face on the threshold may fall either way, but always the same way.
+ * Derivation of k_n (k_closest_surface.hip), in units of u, for |m| = 1 (everything scales with |m|).  The record holds the
+ * orthonormal in-plane frame u, w of the longest edge, formed in f64 and rounded once: every component is off by at most 1
+ * (|component| <= 1).  The corner rotation of the record is cyclic, so u x w is the face normal in the orientation of `faces`:
+ * (B - A) x (C - A) = L t (u x w).  n = u x w is formed per component as fma(a, b, -(c d)): the two products of perturbed inputs
+ * carry 4, the two roundings (the product c d, the fused result; both numbers <= 1) 2: 6 per component.  s = n . m is a
+ * three-term fma chain: the components' 6 weighted by |m_c|, at most 6 sqrt 3 = 10.4, and its own three roundings of partial
+ * sums <= |m|, 3.  Total 13.4 against the f64 normal of the record, stated as k_n = 16; the f64 frame itself is exact to 2^-52
+ * over the relative height, nothing beside u for any face a scan can tell from a segment.  The gate only REMOVES candidates
+ * between the cull and the evaluation, so the cull argument above stands unchanged: a culled triangle's computed distance is
+ * above a running best that is the distance of an admitted candidate.
+ * Checks, workspace, asynchrony and the no-op rules are those of bodyfit_closest_surface_device; also BODYFIT_ERR_INVALID for a
+ * NULL d_query_normals when there are query rows.                                                                            */
+int bodyfit_closest_surface_oriented_device(bodyfit_surface* s, const bodyfit_pointset* query, const float* d_query_normals,
+                                            float min_cos, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                            long long n_query_total, float* d_dist2, int32_t* d_index, float* d_bary,
+                                            int prepare_vjp, void* stream);
 /* Reverse-mode gradient at the fixed correspondence (d_index and d_bary held; by the envelope theorem the true gradient of the
  * squared distance almost everywhere, since the weights minimise): with c^_i = sum_a b_ia v_faces[index_i][a],
  *   d_grad_query[i] = 2 g_i (p_i - c^_i),     d_grad_verts[f][v] = sum over (i, a) with faces[index_i][a] = v of -2 g_i b_ia (p_i - c^_i),

@@ -5,6 +5,10 @@ closest_points at the same sizes (points -> vertices, with prepare_vjp, and its 
 point-triangle evaluation (three clamped edge projections and the interior projection per pair, min over the faces), timed on at
 most --torch-frames frames and reported per frame.  The fused forward is timed WITH prepare_vjp (what a training step pays) and
 without.  Also printed: the ratio to closest_points and triangle tests (pairs) per second.
+The ORIENTED search (bodyfit_closest_surface_oriented_device) is timed in the same run on the same points, search only like
+surface_search_only_us, with the direction of every point the normal of the face it was generated on and min_cos = 0 and 0.5;
+beside each time the share of points that found a compatible triangle and the share whose triangle differs from the
+unoriented search's.
 The share of pairs the sphere cull removes is NOT read from the kernel (a counter would sit in its inner loop): it is a HOST
 REPLAY in numpy of the kernel's order and f32 arithmetic for one workgroup, the first 256 queries of frame 0 without a split
 (the f32 form is the one the tests check against the contract, tests/surface_ref.py, which is why this tool imports it): per pair
@@ -182,6 +186,12 @@ def main():
         ix = torch.empty(F * N, dtype=torch.int32, device="cuda")
         bary = torch.empty((F * N, 3), dtype=torch.float32, device="cuda")
         g = torch.randn(F * N, generator=gen, device="cuda")
+        # directions: the unit normal of the generating face (a face without area: +z)
+        e1, e2 = corners[:, :, 1] - corners[:, :, 0], corners[:, :, 2] - corners[:, :, 0]
+        nrm = torch.linalg.cross(e1, e2)
+        ln = nrm.norm(dim=2, keepdim=True)
+        nrm = torch.where(ln > 0, nrm / ln.clamp(min=1e-30), torch.tensor([0.0, 0.0, 1.0], device="cuda")).contiguous()
+        od2, oix, obary = torch.empty_like(d2), torch.empty_like(ix), torch.empty_like(bary)
         gq, gv = torch.empty_like(pts), torch.empty_like(verts)
 
         def s_fwd_plain():
@@ -190,6 +200,12 @@ def main():
         def s_fwd():
             surf.closest_device(qs, verts.data_ptr(), 3 * V, F, F * N, d2.data_ptr(), ix.data_ptr(), bary.data_ptr(), sp,
                                 prepare_vjp=True)
+
+        def s_oriented(min_cos):
+            def fn():
+                surf.closest_oriented_device(qs, nrm.data_ptr(), min_cos, verts.data_ptr(), 3 * V, F, F * N, od2.data_ptr(),
+                                             oix.data_ptr(), obary.data_ptr(), sp)
+            return fn
 
         def s_bwd():
             surf.vjp_device(qs, verts.data_ptr(), 3 * V, F, F * N, ix.data_ptr(), bary.data_ptr(), g.data_ptr(), gq.data_ptr(),
@@ -212,6 +228,12 @@ def main():
                 t_out[f] = torch_surface(torch, pts[f], verts[f], faces_t, a.torch_chunk)
 
         us_sp = timed(s_fwd_plain)
+        oriented = {}
+        for mc in (0.0, 0.5):
+            us_o = timed(s_oriented(mc))
+            torch.cuda.synchronize()
+            oriented[mc] = (us_o, float((oix >= 0).float().mean()), float((oix != ix).float().mean()))
+        us_sp2 = timed(s_fwd_plain)      # the unoriented search once more, after the oriented ones: the spread of this run
         us_sf, us_sb = timed(s_fwd), timed(s_bwd)
         us_pf, us_pb = timed(p_fwd), timed(p_bwd)
         us_t = timed(t_fwd) / Ft
@@ -224,6 +246,12 @@ def main():
                "surface_search_only_us": round(us_sp, 1), "surface_forward_us": round(us_sf, 1), "surface_backward_us": round(us_sb, 1),
                "points_forward_us": round(us_pf, 1), "points_backward_us": round(us_pb, 1),
                "forward_ratio_to_closest_points": round(us_sf / us_pf, 2), "backward_ratio_to_closest_points": round(us_sb / us_pb, 2),
+               "surface_search_only_us_repeated": round(us_sp2, 1),
+               "oriented_search_only_us_min_cos_0": round(oriented[0.0][0], 1),
+               "oriented_search_only_us_min_cos_0.5": round(oriented[0.5][0], 1),
+               "oriented_share_matched_min_cos_0": round(oriented[0.0][1], 4), "oriented_share_matched_min_cos_0.5": round(oriented[0.5][1], 4),
+               "oriented_share_other_triangle_min_cos_0": round(oriented[0.0][2], 4),
+               "oriented_share_other_triangle_min_cos_0.5": round(oriented[0.5][2], 4),
                "triangle_gpairs_per_s": round(pairs / us_sp * 1e-3, 1),
                "point_gpairs_per_s": round(float(F) * N * V / us_pf * 1e-3, 1),
                "torch_forward_us_per_frame": round(us_t, 1), "torch_frames_timed": Ft,
@@ -234,7 +262,7 @@ def main():
         line = json.dumps(row)
         print(line, flush=True)
         lines.append(line)
-        del verts, pts, corners, d2, ix, bary, g, gq, gv, pd2, pix, t_out
+        del verts, pts, corners, d2, ix, bary, g, gq, gv, pd2, pix, t_out, nrm, od2, oix, obary, e1, e2, ln
         torch.cuda.empty_cache()
     if a.out:
         with open(os.path.join(ROOT, a.out) if not os.path.isabs(a.out) else a.out, "w") as fh:
