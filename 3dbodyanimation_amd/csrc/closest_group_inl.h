@@ -1,10 +1,14 @@
-// closest_group_inl.h — what the closest-point search (k_closest.hip) and the closest-surface search (k_closest_surface.hip)
-// share: the per-frame point-set convention, the (value, index) order of the minimum folds, and the grouping of the queries by
-// the reference row they chose (rows = reference points there, faces here), which the scatter-free backward of either needs.
-// Included once per translation unit; everything has internal linkage.  Besides the kernels it holds the host helpers both
-// ABIs use (check_set, reserve, build_grouping).  build_grouping is a template over the caller's handle struct and uses these
-// members of it, nothing else: `char* ws` (scratch that already holds group_scratch_bytes(nq)), `Grouping groupings[kGroupings]`
-// and `unsigned long long tick` (the least-recently-used clock of the slots).
+// closest_group_inl.h — the skeleton the closest-point search (k_closest.hip) and the closest-surface search
+// (k_closest_surface.hip) share; either file keeps what is specific to its search.  Included once per translation unit;
+// everything has internal linkage.  Device: the per-frame point-set convention; the numbering of the query tiles
+// (BODYFIT_QUERY_TILE); the (value, index) order of every minimum fold (better) and the folds over the waves of a workgroup and
+// over the blockIdx.y splits (fold_waves, fold_splits); the grouping of the queries by the reference row they chose (rows =
+// reference points there, faces here), which the scatter-free backward of either needs.  Host: check_set, reserve, and
+// ClosestWorkspace, the part of either handle that the helpers for the device, the tile count, the split, the scratch and the
+// kept groupings work on.
+// What rests on these pieces alone: index is the LOWEST index of the minimum whatever the split, the wave a candidate fell to
+// and the other frames hold (a minimum by `better` does not depend on how the set was partitioned), and every summation order
+// of a backward is a function of the frame's own data.
 //
 // Grouping: the queries grouped by reference row, each group in ascending query order: a stable counting sort of the index,
 // which depends on the index alone.  INTEGER atomics give a count per row and an arrival slot per query (k_cp_group_count); a
@@ -28,6 +32,11 @@ namespace bodyfit {
 
 namespace {
 
+constexpr int kQ = 4;                 // queries per lane
+constexpr int kWaves = 4;             // waves per workgroup; they share the queries and split every reference tile
+constexpr int kTileQ = 64 * kQ;       // queries per workgroup (BODYFIT_QUERY_TILE on the device, query_tiles on the host)
+constexpr int kMaxSplit = 32;         // splits of the reference range over blockIdx.y
+constexpr int kMinPerSplit = 256;     // reference rows a split should at least have
 constexpr int kHeavy = 64;            // queries per reference row above which the wave sums the row together
 
 struct PointSet {
@@ -68,6 +77,62 @@ __device__ __forceinline__ int frame_of(const PointSet& s, int F, long long row)
 // (d, i) replaces (bd, bi): smaller value, then lower index (-1, "none", is the largest as unsigned)
 __device__ __forceinline__ bool better(float d, int i, float bd, int bi) {
   return d < bd || (d == bd && (unsigned)i < (unsigned)bi);
+}
+
+// ---- the search skeleton: a workgroup of kWaves waves owns the kTileQ queries of one tile of one frame --------------------
+// This workgroup's frame and query tile, into the caller's `int f, tile`.  Ragged: frame f owns the tile numbers offset[f] / kTileQ
+// + f up to those of f + 1 (at least as many as it has tiles; the grid is nq_total / kTileQ + F wide, the spare ones leave at
+// once: q0 >= the frame's count).  A macro on purpose: as a function the numbering is simplified on its own before it is inlined,
+// and both search kernels then come out with another scalar prologue than with the text in place.
+#define BODYFIT_QUERY_TILE(q, F, f, tile)                                    \
+  if ((q).offset) {                                                          \
+    const int b = blockIdx.x;                                                \
+    int lo = 0, hi = (F);                                                    \
+    while (hi - lo > 1) {                                                    \
+      const int mid = (lo + hi) >> 1;                                        \
+      if ((q).offset[mid] / kTileQ + mid <= b) lo = mid; else hi = mid;      \
+    }                                                                        \
+    f = lo; tile = b - ((q).offset[lo] / kTileQ + lo);                       \
+  } else {                                                                   \
+    const int tpf = ((q).n + kTileQ - 1) / kTileQ;                           \
+    f = blockIdx.x / tpf; tile = blockIdx.x - f * tpf;                       \
+  }
+
+// The waves hold the same queries (lane l of every wave: q0 + l, q0 + 64 + l, ...) and each its own share of the candidates:
+// they meet in LDS and thread tid folds query q0 + tid by (value, index).  False: the frame has no such query.
+__device__ __forceinline__ bool fold_waves(float (&s_d)[kWaves][kTileQ], int (&s_i)[kWaves][kTileQ], const float (&best)[kQ],
+                                           const int (&bi)[kQ], int wave, int lane, int tid, int q0, int count, float* out_d,
+                                           int* out_i) {
+#pragma unroll
+  for (int k = 0; k < kQ; ++k) {
+    s_d[wave][k * 64 + lane] = best[k];
+    s_i[wave][k * 64 + lane] = bi[k];
+  }
+  __syncthreads();
+  if (q0 + tid >= count) return false;
+  float bd = s_d[0][tid];
+  int bx = s_i[0][tid];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) {
+    const float d = s_d[w][tid];
+    const int i = s_i[w][tid];
+    if (better(d, i, bd, bx)) { bd = d; bx = i; }
+  }
+  *out_d = bd; *out_i = bx;
+  return true;
+}
+
+// the partial minima of the blockIdx.y splits, [n_split][nq_total], and their fold in the same (value, index) order
+__device__ __forceinline__ void fold_splits(const float* part_d, const int* part_i, int n_split, long long nq_total, long long row,
+                                            float* out_d, int* out_i) {
+  float bd = part_d[row];
+  int bx = part_i[row];
+  for (int s = 1; s < n_split; ++s) {
+    const float d = part_d[(size_t)s * (size_t)nq_total + row];
+    const int i = part_i[(size_t)s * (size_t)nq_total + row];
+    if (better(d, i, bd, bx)) { bd = d; bx = i; }
+  }
+  *out_d = bd; *out_i = bx;
 }
 
 // ---- grouping of the queries by reference row (a function of the index alone: built once per correspondence) ------------
@@ -241,11 +306,74 @@ int reserve(char** p, size_t* have, size_t bytes) {
 
 size_t group_scratch_bytes(long long nq) { return 3 * align256((size_t)nq * 4 + 4) + 256; }
 
+// what bodyfit_closest and bodyfit_surface both hold, and all the host helpers below work on
+struct ClosestWorkspace {
+  int device = 0;
+  int n_cu = 256;
+  char* ws = nullptr;      // scratch of one call: the splits' partial minima, then the grouping's scratch
+  size_t ws_bytes = 0;
+  Grouping groupings[kGroupings];
+  unsigned long long tick = 0;   // the least-recently-used clock of the slots
+};
+
+// makes `device` current and reads its compute-unit count into a fresh workspace
+int open_workspace(const char* fn, int device, ClosestWorkspace* w) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return bodyfit_internal_fail(BODYFIT_ERR_HIP, (std::string(fn) + ": no such HIP device (there is no CPU path)").c_str());
+  HIP_TRY(hipSetDevice(device));
+  int n_cu = 0;
+  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  w->device = device;
+  w->n_cu = n_cu > 0 ? n_cu : 256;
+  return 0;
+}
+
+void release_workspace(ClosestWorkspace* w) {
+  if (w->ws) (void)hipFree(w->ws);
+  for (Grouping& g : w->groupings)
+    if (g.buf) (void)hipFree(g.buf);
+}
+
+// the width of the search grid (the numbering of BODYFIT_QUERY_TILE), or the failure
+int query_tiles(const char* fn, const bodyfit_pointset* query, long long nq, int F, long long* tiles) {
+  *tiles = query->d_offset ? nq / kTileQ + F : (long long)F * ((query->n_per_frame + kTileQ - 1) / kTileQ);
+  if (*tiles >= (1LL << 31)) return invalid(fn, "too many query tiles");
+  return 0;
+}
+
+// few query tiles: split the frame's reference rows until the device has about four workgroups per compute unit
+int choose_split(int n_cu, long long tiles, long long rows_per_frame) {
+  long long split = (4LL * n_cu + tiles - 1) / tiles;
+  if (split > rows_per_frame / kMinPerSplit) split = rows_per_frame / kMinPerSplit;
+  if (split > kMaxSplit) split = kMaxSplit;
+  return split < 1 ? 1 : (int)split;
+}
+
+// The scratch of one search: the partial minima of n_split > 1 splits, part_d and part_i (else left as they are), and, with
+// `group`, room for the grouping's scratch, which may lie over them: the grouping runs behind the fold on the stream.
+int reserve_search_scratch(ClosestWorkspace* w, int n_split, long long nq, bool group, float** part_d, int** part_i) {
+  const size_t part = n_split > 1 ? align256((size_t)n_split * (size_t)nq * 4) : 0;
+  size_t need = 2 * part;
+  if (group && group_scratch_bytes(nq) > need) need = group_scratch_bytes(nq);
+  if (int rc = reserve(&w->ws, &w->ws_bytes, need)) return rc;
+  if (n_split > 1) {
+    *part_d = reinterpret_cast<float*>(w->ws);
+    *part_i = reinterpret_cast<int*>(w->ws + part);
+  }
+  return 0;
+}
+
+// d_index is about to change: a grouping kept for this pointer is void
+void invalidate(ClosestWorkspace* w, const void* d_index) {
+  for (Grouping& g : w->groupings)
+    if (g.index == d_index) g.valid = false;
+}
+
 // Builds the grouping of d_index on `st` into the slot that held this index before, else the least recently used one.  The
-// handle's scratch must already hold group_scratch_bytes(nq).  keep: later VJP calls with this d_index may use it.
-template <class Handle>
-int build_grouping(Handle* h, const bodyfit_pointset* query, const bodyfit_pointset* ref, int F, long long nq,
-                   long long nr, const int32_t* d_index, bool keep, hipStream_t st, bodyfit::Grouping** out) {
+// workspace's scratch must already hold group_scratch_bytes(nq).  keep: later VJP calls with this d_index may use it.
+int build_grouping(ClosestWorkspace* h, const bodyfit_pointset* query, const bodyfit_pointset* ref, int F, long long nq,
+                   long long nr, const int32_t* d_index, bool keep, hipStream_t st, Grouping** out) {
   Grouping* g = nullptr;
   for (Grouping& c : h->groupings)
     if (c.index == d_index) { g = &c; break; }
@@ -287,6 +415,20 @@ int build_grouping(Handle* h, const bodyfit_pointset* query, const bodyfit_point
   g->valid = keep;
   *out = g;
   return 0;
+}
+
+// the grouping a search kept for this correspondence, or, where none prepared it, one built now for this call only
+int kept_or_built_grouping(ClosestWorkspace* w, const bodyfit_pointset* query, const bodyfit_pointset* ref, int F, long long nq,
+                           long long nr, const int32_t* d_index, hipStream_t st, Grouping** out) {
+  *out = nullptr;
+  for (Grouping& c : w->groupings)
+    if (c.matches(d_index, query, ref, F, nq, nr)) *out = &c;
+  if (*out) {
+    (*out)->used = ++w->tick;
+    return 0;
+  }
+  if (int rc = reserve(&w->ws, &w->ws_bytes, group_scratch_bytes(nq))) return rc;
+  return build_grouping(w, query, ref, F, nq, nr, d_index, false, st, out);
 }
 
 }  // namespace

@@ -12,18 +12,17 @@
 // address (one broadcast LDS read, compiled to ds_read_b96, feeds 256 distance evaluations).  A distance is the difference form
 // (px - cx)^2 + (py - cy)^2 + (pz - cz)^2 in f32 — the expansion form loses the digits at camera-frame magnitudes — and a
 // candidate replaces the running minimum on `<` only, in ascending index order, so equal distances keep the lowest index and a
-// NaN never wins.  The four waves' results meet in LDS, reduced by (value, then index).  With few query tiles (one frame, or a
-// few markers per frame) the reference range is also split over blockIdx.y; the splits leave partial (min, argmin) rows that
-// k_closest_reduce folds in the same (value, index) order.  The minimum of a set and its lowest index do not depend on how the
-// set was partitioned, so the outputs are bit-identical whatever the split, the frame count and the other frames hold.
+// NaN never wins.  The four waves' results meet in LDS; with few query tiles (one frame, or a few markers per frame) the
+// reference range is also split over blockIdx.y and k_closest_reduce folds the splits' partial rows: every fold is by (value,
+// then index), so the outputs are bit-identical whatever the split, the frame count and the other frames hold.
 // Ragged sets: offset[0] = 0 and offset[F] = the set's row count (the tile numbering and the packed rows rely on it).
 //
 // Backward (k_cp_vjp, one launch): dL/dquery_i = -2 g_i (c_index_i - p_i) is one thread per query.  dL/dref_v sums over the
 // queries that chose v, in f32, without float atomics and in a fixed order: one thread per reference row in ascending query
-// order, or, for a row more than 64 queries chose, the whole wave with lane l taking entries l, l + 64, ... in ascending order
-// followed by a fixed butterfly.  Either order is a function of the frame's own data only.
+// order, or the whole wave for a row more than 64 queries chose.  Either order is a function of the frame's own data only.
 //
-// The point-set convention, the fold order and the grouping live in closest_group_inl.h: the closest-surface search shares them.
+// The point-set convention, the tile numbering, the folds, the grouping and the host side of the workspace live in
+// closest_group_inl.h: the closest-surface search shares them.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -42,13 +41,8 @@ namespace bodyfit {
 
 namespace {
 
-constexpr int kQ = 4;                 // queries per lane
-constexpr int kWaves = 4;             // waves per workgroup; they share the queries and split every reference tile
-constexpr int kTileQ = 64 * kQ;       // queries per workgroup
 constexpr int kTileR = 1024;          // reference points per LDS tile (16 KB as float4)
 constexpr int kGroup = 4;             // reference points a wave takes at a time
-constexpr int kMaxSplit = 32;         // splits of the reference range over blockIdx.y
-constexpr int kMinPerSplit = 256;     // reference points a split should at least have
 
 struct ClosestArgs {
   PointSet q, r;
@@ -64,21 +58,8 @@ __global__ __launch_bounds__(64 * kWaves) void k_closest(const ClosestArgs a) {
   __shared__ int s_i[kWaves][kTileQ];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // this workgroup's frame and query tile.  Ragged: frame f owns the tile numbers offset[f] / kTileQ + f up to those of f + 1
-  // (at least as many as it has tiles; the grid is nq_total / kTileQ + F wide, the spare ones leave at once).
   int f, tile;
-  if (a.q.offset) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = a.F;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.q.offset[mid] / kTileQ + mid <= b) lo = mid; else hi = mid;
-    }
-    f = lo; tile = b - (a.q.offset[lo] / kTileQ + lo);
-  } else {
-    const int tpf = (a.q.n + kTileQ - 1) / kTileQ;
-    f = blockIdx.x / tpf; tile = blockIdx.x - f * tpf;
-  }
+  BODYFIT_QUERY_TILE(a.q, a.F, f, tile)
   const FrameRange fq = frame_range(a.q, f), fr = frame_range(a.r, f);
   const int q0 = tile * kTileQ;
   if (q0 >= fq.count) return;
@@ -130,23 +111,10 @@ __global__ __launch_bounds__(64 * kWaves) void k_closest(const ClosestArgs a) {
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < kQ; ++k) {
-    s_d[wave][k * 64 + lane] = best[k];
-    s_i[wave][k * 64 + lane] = bi[k];
-  }
-  __syncthreads();
-  const int qi = q0 + tid;
-  if (qi >= fq.count) return;
-  float bd = s_d[0][tid];
-  int bx = s_i[0][tid];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) {
-    const float d = s_d[w][tid];
-    const int i = s_i[w][tid];
-    if (better(d, i, bd, bx)) { bd = d; bx = i; }
-  }
-  const size_t row = (size_t)(fq.row0 + qi);
+  float bd;
+  int bx;
+  if (!fold_waves(s_d, s_i, best, bi, wave, lane, tid, q0, fq.count, &bd, &bx)) return;
+  const size_t row = (size_t)(fq.row0 + (q0 + tid));
   if (a.n_split > 1) {
     a.part_d[(size_t)blockIdx.y * (size_t)a.nq_total + row] = bd;
     a.part_i[(size_t)blockIdx.y * (size_t)a.nq_total + row] = bx;
@@ -159,13 +127,9 @@ __global__ __launch_bounds__(64 * kWaves) void k_closest(const ClosestArgs a) {
 __global__ __launch_bounds__(256) void k_closest_reduce(const ClosestArgs a) {
   const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
   if (row >= a.nq_total) return;
-  float bd = a.part_d[row];
-  int bx = a.part_i[row];
-  for (int s = 1; s < a.n_split; ++s) {
-    const float d = a.part_d[(size_t)s * (size_t)a.nq_total + row];
-    const int i = a.part_i[(size_t)s * (size_t)a.nq_total + row];
-    if (better(d, i, bd, bx)) { bd = d; bx = i; }
-  }
+  float bd;
+  int bx;
+  fold_splits(a.part_d, a.part_i, a.n_split, a.nq_total, row, &bd, &bx);
   a.dist2[row] = bd;
   a.index[row] = bx;
 }
@@ -259,39 +223,22 @@ __global__ __launch_bounds__(256) void k_cp_vjp(const VjpArgs a) {
 
 }  // namespace bodyfit
 
-struct bodyfit_closest {
-  int device = 0;
-  int n_cu = 256;
-  char* ws = nullptr;      // scratch of one call: the splits' partial minima, then the grouping's scratch
-  size_t ws_bytes = 0;
-  bodyfit::Grouping groupings[bodyfit::kGroupings];
-  unsigned long long tick = 0;
-};
-
+struct bodyfit_closest { bodyfit::ClosestWorkspace w; };
 
 extern "C" {
 
 int bodyfit_closest_create(int device, bodyfit_closest** out) {
   if (!out) return bodyfit::invalid("bodyfit_closest_create", "null argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return bodyfit_internal_fail(BODYFIT_ERR_HIP, "bodyfit_closest_create: no such HIP device (there is no CPU path)");
-  HIP_TRY(hipSetDevice(device));
-  int n_cu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-  bodyfit_closest* h = new bodyfit_closest;
-  h->device = device;
-  h->n_cu = n_cu > 0 ? n_cu : 256;
-  *out = h;
+  bodyfit::ClosestWorkspace w;
+  if (int rc = bodyfit::open_workspace("bodyfit_closest_create", device, &w)) return rc;
+  *out = new bodyfit_closest{w};
   return BODYFIT_OK;
 }
 
 void bodyfit_closest_destroy(bodyfit_closest* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->ws) (void)hipFree(h->ws);
-  for (bodyfit::Grouping& g : h->groupings)
-    if (g.buf) (void)hipFree(g.buf);
+  (void)hipSetDevice(h->w.device);
+  bodyfit::release_workspace(&h->w);
   delete h;
 }
 
@@ -306,42 +253,24 @@ int bodyfit_closest_points_device(bodyfit_closest* h, const bodyfit_pointset* qu
   if (!d_dist2 || !d_index) return invalid(fn, "d_dist2 / d_index is NULL");
   if (!h) return invalid(fn, "null handle");
   if (n_frames == 0 || n_query_total == 0) return BODYFIT_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->w.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // d_index is about to change: a grouping kept for this pointer is void
-  for (Grouping& g : h->groupings)
-    if (g.index == d_index) g.valid = false;
+  invalidate(&h->w, d_index);
   ClosestArgs a{};
   a.q = device_set(query); a.r = device_set(ref);
   a.F = n_frames; a.nq_total = n_query_total;
   a.dist2 = d_dist2; a.index = d_index;
-  const long long tiles = query->d_offset ? n_query_total / kTileQ + n_frames
-                                          : (long long)n_frames * ((query->n_per_frame + kTileQ - 1) / kTileQ);
-  if (tiles >= (1LL << 31)) return invalid(fn, "too many query tiles");
-  // few query tiles: split the reference range until the device has about four workgroups per compute unit
-  const long long ref_per_frame = ref->d_offset ? (n_ref_total + n_frames - 1) / n_frames : ref->n_per_frame;
-  long long split = (4LL * h->n_cu + tiles - 1) / tiles;
-  if (split > ref_per_frame / kMinPerSplit) split = ref_per_frame / kMinPerSplit;
-  if (split > kMaxSplit) split = kMaxSplit;
-  if (split < 1) split = 1;
-  a.n_split = (int)split;
+  long long tiles;
+  if (int rc = query_tiles(fn, query, n_query_total, n_frames, &tiles)) return rc;
+  a.n_split = choose_split(h->w.n_cu, tiles, ref->d_offset ? (n_ref_total + n_frames - 1) / n_frames : ref->n_per_frame);
   const bool group = prepare_vjp && n_ref_total > 0;
-  const size_t part = a.n_split > 1 ? align256((size_t)a.n_split * (size_t)n_query_total * 4) : 0;
-  size_t need = 2 * part;
-  if (group && group_scratch_bytes(n_query_total) > need) need = group_scratch_bytes(n_query_total);
-  if (int rc = reserve(&h->ws, &h->ws_bytes, need)) return rc;
-  if (a.n_split > 1) {
-    a.part_d = reinterpret_cast<float*>(h->ws);
-    a.part_i = reinterpret_cast<int*>(h->ws + part);
-  }
+  if (int rc = reserve_search_scratch(&h->w, a.n_split, n_query_total, group, &a.part_d, &a.part_i)) return rc;
   BODYFIT_LAUNCH(k_closest, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kWaves), 0, st, a);
   if (a.n_split > 1)
     BODYFIT_LAUNCH(k_closest_reduce, dim3((unsigned)((n_query_total + 255) / 256)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
-  if (group) {   // (behind the reduction on the stream: the scratch may lie over the partial minima)
-    Grouping* g = nullptr;
-    if (int rc = build_grouping(h, query, ref, n_frames, n_query_total, n_ref_total, d_index, true, st, &g)) return rc;
-  }
+  Grouping* g = nullptr;   // (behind the reduction on the stream: the scratch may lie over the partial minima)
+  if (group) return build_grouping(&h->w, query, ref, n_frames, n_query_total, n_ref_total, d_index, true, st, &g);
   return BODYFIT_OK;
 }
 
@@ -357,7 +286,7 @@ int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset
   if (!h) return invalid(fn, "null handle");
   if (n_frames == 0 || (!d_grad_query && !d_grad_ref)) return BODYFIT_OK;
   if (n_query_total == 0 && (!d_grad_ref || n_ref_total == 0)) return BODYFIT_OK;
-  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipSetDevice(h->w.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   VjpArgs a{};
   a.q = device_set(query); a.r = device_set(ref);
@@ -367,14 +296,7 @@ int bodyfit_closest_points_vjp_device(bodyfit_closest* h, const bodyfit_pointset
   const unsigned rblocks = a.gr ? (unsigned)((n_ref_total + 255) / 256) : 0u;
   if (a.gr) {
     Grouping* g = nullptr;
-    for (Grouping& c : h->groupings)
-      if (c.matches(d_index, query, ref, n_frames, n_query_total, n_ref_total)) g = &c;
-    if (g) {
-      g->used = ++h->tick;
-    } else {   // no forward prepared this correspondence: group now, for this call only
-      if (int rc = reserve(&h->ws, &h->ws_bytes, group_scratch_bytes(n_query_total))) return rc;
-      if (int rc = build_grouping(h, query, ref, n_frames, n_query_total, n_ref_total, d_index, false, st, &g)) return rc;
-    }
+    if (int rc = kept_or_built_grouping(&h->w, query, ref, n_frames, n_query_total, n_ref_total, d_index, st, &g)) return rc;
     a.cnt = g->cnt; a.start = g->start; a.sorted = g->sorted;
   }
   if (a.qblocks + rblocks) BODYFIT_LAUNCH(k_cp_vjp, dim3(a.qblocks + rblocks), dim3(256), 0, st, a);

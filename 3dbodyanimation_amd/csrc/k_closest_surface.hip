@@ -16,9 +16,9 @@
 // give t = 0, w = 0 (the face is the segment AB, which contains C since AB is the longest edge), a point gives L = 0, u = 0.
 // A face with a non-finite corner gets R = NaN and is never looked at.
 //
-// Search (k_cs_search): the layout of k_closest — a workgroup of four waves owns 256 queries of one frame, every lane four of
-// them with their running (min, argmin) in registers, records go through LDS 256 at a time and are read back at wave-uniform
-// addresses, the waves take a tile's records in turn and meet in LDS by (value, index).  Per pair, in f32:
+// Search (k_cs_search): the skeleton of closest_group_inl.h, as in k_closest — a workgroup of four waves owns 256 queries of one
+// frame, every lane four of them with their running (min, argmin) in registers, records go through LDS 256 at a time and are read
+// back at wave-uniform addresses, the waves take a tile's records in turn and meet in LDS by (value, index).  Per pair, in f32:
 //   ap = p - A;  X = ap . u;  cull: |ap - (L/2) u|^2 > (sqrt(best) (1 + 2^-12) + R)^2 -> next triangle;
 //   Y = ap . w;  the closest point (qx, qy) of the 2-D triangle to (X, Y): (X, Y) itself when the three edge functions say
 //   inside (Ericson's interior region), else the nearest of the projections onto the three edges, each clamped to its segment
@@ -56,12 +56,7 @@ namespace bodyfit {
 
 namespace {
 
-constexpr int kSQ = 4;                // queries per lane
-constexpr int kSWaves = 4;            // waves per workgroup; they share the queries and split every tile of records
-constexpr int kSTileQ = 64 * kSQ;     // queries per workgroup
 constexpr int kSTileT = 256;          // triangle records per LDS tile (16 KB)
-constexpr int kSMaxSplit = 32;        // splits of the face range over blockIdx.y
-constexpr int kSMinPerSplit = 256;    // faces a split should at least have
 constexpr float kCullInflate = 1.0f + 1.0f / 4096.0f;
 
 struct SurfArgs {
@@ -193,34 +188,22 @@ __device__ __forceinline__ float eval_tri(float ax, float ay, float az, float X,
 // without a height (t = 0) has no normal and is never a candidate.  The gate sits between the cull and the evaluation and only
 // removes candidates, so the cull argument stands; everything written with `if constexpr` is absent from the other instantiation.
 template <bool kOriented>
-__global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
+__global__ __launch_bounds__(64 * kWaves) void k_cs_search(const SurfArgs a) {
   __shared__ float4 s_rec[4 * kSTileT];
-  __shared__ float s_d[kSWaves][kSTileQ];
-  __shared__ int s_i[kSWaves][kSTileQ];
+  __shared__ float s_d[kWaves][kTileQ];
+  __shared__ int s_i[kWaves][kTileQ];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // this workgroup's frame and query tile (the numbering of k_closest)
   int f, tile;
-  if (a.q.offset) {
-    const int b = blockIdx.x;
-    int lo = 0, hi = a.F;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (a.q.offset[mid] / kSTileQ + mid <= b) lo = mid; else hi = mid;
-    }
-    f = lo; tile = b - (a.q.offset[lo] / kSTileQ + lo);
-  } else {
-    const int tpf = (a.q.n + kSTileQ - 1) / kSTileQ;
-    f = blockIdx.x / tpf; tile = blockIdx.x - f * tpf;
-  }
+  BODYFIT_QUERY_TILE(a.q, a.F, f, tile)
   const FrameRange fq = frame_range(a.q, f);
-  const int q0 = tile * kSTileQ;
+  const int q0 = tile * kTileQ;
   if (q0 >= fq.count) return;
-  float px[kSQ], py[kSQ], pz[kSQ], best[kSQ], bs[kSQ];
-  [[maybe_unused]] float mx[kSQ], my[kSQ], mz[kSQ];
-  int bi[kSQ];
+  float px[kQ], py[kQ], pz[kQ], best[kQ], bs[kQ];
+  [[maybe_unused]] float mx[kQ], my[kQ], mz[kQ];
+  int bi[kQ];
 #pragma unroll
-  for (int k = 0; k < kSQ; ++k) {
+  for (int k = 0; k < kQ; ++k) {
     const int qi = q0 + k * 64 + lane;
     const bool ok = qi < fq.count;
     const float* p = a.q.xyz + fq.first + 3 * (size_t)(ok ? qi : q0);
@@ -242,9 +225,9 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
     const int cnt = min(kSTileT, c1 - t0);
     __syncthreads();   // the previous tile has been read by every wave
     const float4* src = rbase + 4 * (size_t)t0;
-    for (int j = tid; j < 4 * cnt; j += 64 * kSWaves) s_rec[j] = src[j];
+    for (int j = tid; j < 4 * cnt; j += 64 * kWaves) s_rec[j] = src[j];
     __syncthreads();
-    for (int j = wave; j < cnt; j += kSWaves) {
+    for (int j = wave; j < cnt; j += kWaves) {
       const float4 r0 = s_rec[4 * j], r1 = s_rec[4 * j + 1], r2 = s_rec[4 * j + 2], r3 = s_rec[4 * j + 3];
       const int ci = t0 + j;
       const float L = r0.w, R = r3.x;
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
         nz = fmaf(r1.x, r2.y, -(r1.y * r2.x));
       }
 #pragma unroll
-      for (int k = 0; k < kSQ; ++k) {
+      for (int k = 0; k < kQ; ++k) {
         const float ax = px[k] - r0.x, ay = py[k] - r0.y, az = pz[k] - r0.z;
         const float ap2 = fmaf(az, az, fmaf(ay, ay, ax * ax));
         const float X = fmaf(az, r1.z, fmaf(ay, r1.y, ax * r1.x));
@@ -277,23 +260,10 @@ __global__ __launch_bounds__(64 * kSWaves) void k_cs_search(const SurfArgs a) {
       }
     }
   }
-#pragma unroll
-  for (int k = 0; k < kSQ; ++k) {
-    s_d[wave][k * 64 + lane] = best[k];
-    s_i[wave][k * 64 + lane] = bi[k];
-  }
-  __syncthreads();
-  const int qi = q0 + tid;
-  if (qi >= fq.count) return;
-  float bd = s_d[0][tid];
-  int bx = s_i[0][tid];
-#pragma unroll
-  for (int w = 1; w < kSWaves; ++w) {
-    const float d = s_d[w][tid];
-    const int i = s_i[w][tid];
-    if (better(d, i, bd, bx)) { bd = d; bx = i; }
-  }
-  const size_t row = (size_t)(fq.row0 + qi);
+  float bd;
+  int bx;
+  if (!fold_waves(s_d, s_i, best, bi, wave, lane, tid, q0, fq.count, &bd, &bx)) return;
+  const size_t row = (size_t)(fq.row0 + (q0 + tid));
   if (a.n_split > 1) {
     a.part_d[(size_t)blockIdx.y * (size_t)a.nq_total + row] = bd;
     a.part_i[(size_t)blockIdx.y * (size_t)a.nq_total + row] = bx;
@@ -308,13 +278,8 @@ __global__ __launch_bounds__(256) void k_cs_finish(const SurfArgs a) {
   if (row >= a.nq_total) return;
   int bx;
   if (a.n_split > 1) {
-    float bd = a.part_d[row];
-    bx = a.part_i[row];
-    for (int s = 1; s < a.n_split; ++s) {
-      const float d = a.part_d[(size_t)s * (size_t)a.nq_total + row];
-      const int i = a.part_i[(size_t)s * (size_t)a.nq_total + row];
-      if (better(d, i, bd, bx)) { bd = d; bx = i; }
-    }
+    float bd;
+    fold_splits(a.part_d, a.part_i, a.n_split, a.nq_total, row, &bd, &bx);
     a.index[row] = bx;
   } else {
     bx = a.index[row];
@@ -470,8 +435,7 @@ __global__ __launch_bounds__(256) void k_cs_vjp_verts(const SurfVjpArgs a) {
 }  // namespace bodyfit
 
 struct bodyfit_surface {
-  int device = 0;
-  int n_cu = 256;
+  bodyfit::ClosestWorkspace w;
   int n_verts = 0, n_faces = 0;
   int* d_faces = nullptr;      // [n_faces][3]
   int* d_csr_off = nullptr;    // [n_verts + 1]
@@ -480,10 +444,6 @@ struct bodyfit_surface {
   size_t rec_bytes = 0;
   char* acc = nullptr;         // per-face corner sums of a backward
   size_t acc_bytes = 0;
-  char* ws = nullptr;          // scratch of one call: the splits' partial minima, then the grouping's scratch
-  size_t ws_bytes = 0;
-  bodyfit::Grouping groupings[bodyfit::kGroupings];
-  unsigned long long tick = 0;
 };
 
 namespace {
@@ -525,15 +485,10 @@ int bodyfit_surface_create(int device, int n_verts, int n_faces, const int32_t* 
     std::vector<int> at(off.begin(), off.end() - 1);
     for (size_t k = 0; k < 3 * (size_t)n_faces; ++k) fc[at[faces[k]]++] = (int)k;   // ascending 3 face + corner
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return bodyfit_internal_fail(BODYFIT_ERR_HIP, "bodyfit_surface_create: no such HIP device (there is no CPU path)");
-  HIP_TRY(hipSetDevice(device));
-  int n_cu = 0;
-  HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  ClosestWorkspace w;
+  if (int rc = open_workspace(fn, device, &w)) return rc;
   bodyfit_surface* s = new bodyfit_surface;
-  s->device = device;
-  s->n_cu = n_cu > 0 ? n_cu : 256;
+  s->w = w;
   s->n_verts = n_verts; s->n_faces = n_faces;
   const size_t fb = 3 * (size_t)n_faces * 4, ob = ((size_t)n_verts + 1) * 4;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_faces), fb + 4);
@@ -552,11 +507,10 @@ int bodyfit_surface_create(int device, int n_verts, int n_faces, const int32_t* 
 
 void bodyfit_surface_destroy(bodyfit_surface* s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);
-  for (void* p : {(void*)s->d_faces, (void*)s->d_csr_off, (void*)s->d_csr_fc, (void*)s->rec, (void*)s->acc, (void*)s->ws})
+  (void)hipSetDevice(s->w.device);
+  for (void* p : {(void*)s->d_faces, (void*)s->d_csr_off, (void*)s->d_csr_fc, (void*)s->rec, (void*)s->acc})
     if (p) (void)hipFree(p);
-  for (bodyfit::Grouping& g : s->groupings)
-    if (g.buf) (void)hipFree(g.buf);
+  bodyfit::release_workspace(&s->w);
   delete s;
 }
 
@@ -574,46 +528,32 @@ int closest_surface_call(const char* fn, bool oriented, bodyfit_surface* s, cons
   if (!d_dist2 || !d_index || !d_bary) return invalid(fn, "d_dist2 / d_index / d_bary is NULL");
   if (oriented && n_frames > 0 && n_query_total > 0 && !d_query_normals) return invalid(fn, "d_query_normals is NULL");
   if (n_frames == 0 || n_query_total == 0) return BODYFIT_OK;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->w.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  for (Grouping& g : s->groupings)
-    if (g.index == d_index) g.valid = false;
+  invalidate(&s->w, d_index);
   SurfArgs a{};
   a.q = device_set(query);
   a.verts = d_verts; a.vstride = verts_frame_stride; a.faces = s->d_faces; a.n_faces = s->n_faces;
   a.F = n_frames; a.nq_total = n_query_total;
   a.dist2 = d_dist2; a.index = d_index; a.bary = d_bary;
   a.qn = d_query_normals; a.min_cos = min_cos;
-  const long long tiles = query->d_offset ? n_query_total / kSTileQ + n_frames
-                                          : (long long)n_frames * ((query->n_per_frame + kSTileQ - 1) / kSTileQ);
-  if (tiles >= (1LL << 31)) return invalid(fn, "too many query tiles");
-  // few query tiles: split the face range until the device has about four workgroups per compute unit
-  long long split = (4LL * s->n_cu + tiles - 1) / tiles;
-  if (split > s->n_faces / kSMinPerSplit) split = s->n_faces / kSMinPerSplit;
-  if (split > kSMaxSplit) split = kSMaxSplit;
-  if (split < 1) split = 1;
-  a.n_split = (int)split;
+  long long tiles;
+  if (int rc = query_tiles(fn, query, n_query_total, n_frames, &tiles)) return rc;
+  a.n_split = choose_split(s->w.n_cu, tiles, s->n_faces);
   const long long n_rows = (long long)n_frames * s->n_faces;
   const bool group = prepare_vjp && n_rows > 0;
-  const size_t part = a.n_split > 1 ? align256((size_t)a.n_split * (size_t)n_query_total * 4) : 0;
-  size_t need = 2 * part;
-  if (group && group_scratch_bytes(n_query_total) > need) need = group_scratch_bytes(n_query_total);
-  if (int rc = reserve(&s->ws, &s->ws_bytes, need)) return rc;
+  if (int rc = reserve_search_scratch(&s->w, a.n_split, n_query_total, group, &a.part_d, &a.part_i)) return rc;
   if (int rc = reserve(&s->rec, &s->rec_bytes, (size_t)n_rows * 64)) return rc;
   a.rec = reinterpret_cast<float4*>(s->rec);
-  if (a.n_split > 1) {
-    a.part_d = reinterpret_cast<float*>(s->ws);
-    a.part_i = reinterpret_cast<int*>(s->ws + part);
-  }
   if (n_rows > 0) BODYFIT_LAUNCH(k_cs_prepare, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, a);
-  if (oriented) BODYFIT_LAUNCH(k_cs_search<true>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kSWaves), 0, st, a);
-  else BODYFIT_LAUNCH(k_cs_search<false>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kSWaves), 0, st, a);
+  if (oriented) BODYFIT_LAUNCH(k_cs_search<true>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kWaves), 0, st, a);
+  else BODYFIT_LAUNCH(k_cs_search<false>, dim3((unsigned)tiles, (unsigned)a.n_split), dim3(64 * kWaves), 0, st, a);
   BODYFIT_LAUNCH(k_cs_finish, dim3((unsigned)((n_query_total + 255) / 256)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
   if (group) {   // (behind the fold on the stream: the scratch may lie over the partial minima)
     const bodyfit_pointset fr = face_rows(s);
     Grouping* g = nullptr;
-    if (int rc = build_grouping(s, query, &fr, n_frames, n_query_total, n_rows, d_index, true, st, &g)) return rc;
+    return build_grouping(&s->w, query, &fr, n_frames, n_query_total, n_rows, d_index, true, st, &g);
   }
   return BODYFIT_OK;
 }
@@ -647,7 +587,7 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
   if (n_query_total > 0 && (!d_index || !d_bary || !d_grad_dist2)) return invalid(fn, "d_index / d_bary / d_grad_dist2 is NULL");
   if (n_frames == 0 || (!d_grad_query && !d_grad_verts)) return BODYFIT_OK;
   if (n_query_total == 0 && (!d_grad_verts || s->n_verts == 0)) return BODYFIT_OK;
-  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipSetDevice(s->w.device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long n_rows = (long long)n_frames * s->n_faces;
   const bodyfit_pointset fr = face_rows(s);
@@ -664,14 +604,7 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
   unsigned fblocks = 0;
   if (a.gv && n_rows > 0) {
     Grouping* g = nullptr;
-    for (Grouping& c : s->groupings)
-      if (c.matches(d_index, query, &fr, n_frames, n_query_total, n_rows)) g = &c;
-    if (g) {
-      g->used = ++s->tick;
-    } else {   // no search prepared this correspondence: group now, for this call only
-      if (int rc = reserve(&s->ws, &s->ws_bytes, group_scratch_bytes(n_query_total))) return rc;
-      if (int rc = build_grouping(s, query, &fr, n_frames, n_query_total, n_rows, d_index, false, st, &g)) return rc;
-    }
+    if (int rc = kept_or_built_grouping(&s->w, query, &fr, n_frames, n_query_total, n_rows, d_index, st, &g)) return rc;
     a.cnt = g->cnt; a.start = g->start; a.sorted = g->sorted;
     if (int rc = reserve(&s->acc, &s->acc_bytes, (size_t)n_rows * 36)) return rc;
     a.acc = reinterpret_cast<float*>(s->acc);

@@ -277,6 +277,25 @@ def _grad_like(t: torch.Tensor, ps) -> torch.Tensor:
     return torch.empty(t.shape, dtype=torch.float32, device=t.device)
 
 
+def _grads_for(ctx, sets, live: bool):
+    """the gradients of a backward's two point tensors, ((tensor, ps), (tensor, ps)): uninitialised where the VJP kernel will
+    write them (live), zero otherwise, None where ctx needs none"""
+    grads = [_grad_like(t, ps) if want else None for (t, ps), want in zip(sets, ctx.needs_input_grad)]
+    if not live:
+        for g in grads:
+            if g is not None:
+                g.zero_()
+    return grads
+
+
+def _rho_sum(dist2: torch.Tensor, index: torch.Tensor, trunc: float | None) -> torch.Tensor:
+    """the f64 sum of rho(dist2) over the rows with a counterpart (a row without one: index -1, dist2 +inf, costs nothing)"""
+    s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))
+    if trunc is not None:
+        s = torch.clamp(s, max=trunc * trunc)
+    return s.double().sum()
+
+
 class _ClosestPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, query, ref, query_offset, ref_offset):
@@ -303,14 +322,9 @@ class _ClosestPoints(torch.autograd.Function):
     def backward(ctx, g_dist2, _g_index):
         q, r, index = ctx.saved_tensors
         qs, rs, F, nq, nr, handle = ctx.sets
-        want_q, want_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gq = _grad_like(q, qs) if want_q else None
-        gr = _grad_like(r, rs) if want_r else None
-        if g_dist2 is None or nq == 0:
-            for g in (gq, gr):
-                if g is not None:
-                    g.zero_()
-        else:
+        live = g_dist2 is not None and nq > 0
+        gq, gr = _grads_for(ctx, ((q, qs), (r, rs)), live)
+        if live:
             g = g_dist2.to(torch.float32).contiguous()
             handle.points_vjp_device(qs, rs, F, nq, nr, index.data_ptr(), g.data_ptr(),
                                      gq.data_ptr() if gq is not None else None,
@@ -352,16 +366,10 @@ class PointCloudTerm(torch.nn.Module):
         self.bidirectional = bool(bidirectional)
         self.trunc = None if trunc is None else float(trunc)
 
-    def _rho(self, dist2, index):
-        s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))   # (a frame without a counterpart: +inf, costs nothing)
-        if self.trunc is not None:
-            s = torch.clamp(s, max=self.trunc * self.trunc)
-        return s.double().sum()
-
     def forward(self, verts: torch.Tensor) -> torch.Tensor:
-        cost = self._rho(*closest_points(self.points, verts, query_offset=self.offset))
+        cost = _rho_sum(*closest_points(self.points, verts, query_offset=self.offset), self.trunc)
         if self.bidirectional:
-            cost = cost + self._rho(*closest_points(verts, self.points, ref_offset=self.offset))
+            cost = cost + _rho_sum(*closest_points(verts, self.points, ref_offset=self.offset), self.trunc)
         return cost
 
 
@@ -449,14 +457,9 @@ class _ClosestSurface(torch.autograd.Function):
     def backward(ctx, g_dist2, _g_index, _g_bary):
         q, v, index, bary = ctx.saved_tensors
         qs, vs, F, nq, handle = ctx.sets
-        want_q, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gq = _grad_like(q, qs) if want_q else None
-        gv = _grad_like(v, vs) if want_v else None
-        if g_dist2 is None or nq == 0:
-            for g in (gq, gv):
-                if g is not None:
-                    g.zero_()
-        else:
+        live = g_dist2 is not None and nq > 0
+        gq, gv = _grads_for(ctx, ((q, qs), (v, vs)), live)
+        if live:
             g = g_dist2.to(torch.float32).contiguous()
             handle.vjp_device(qs, v.data_ptr(), vs.frame_stride, F, nq, index.data_ptr(), bary.data_ptr(), g.data_ptr(),
                               gq.data_ptr() if gq is not None else None, gv.data_ptr() if gv is not None else None, _stream())
@@ -542,7 +545,4 @@ class SurfaceTerm(torch.nn.Module):
                 faces = self._handles[key] = _surface_handle(key[0], key[1], self.faces)
         dist2, index, _ = closest_surface(self.points, verts, faces, query_offset=self.offset, point_normals=self.normals,
                                           min_cos=self.min_cos)
-        s = torch.where(index >= 0, dist2, torch.zeros_like(dist2))
-        if self.trunc is not None:
-            s = torch.clamp(s, max=self.trunc * self.trunc)
-        return s.double().sum()
+        return _rho_sum(dist2, index, self.trunc)
