@@ -212,6 +212,9 @@ def load_library():
     lib.bodyfit_forward_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_forward_vjp.argtypes = [C.c_void_p, _dp, _dp, _fp, _dp, _dp, _dp]
+    lib.bodyfit_forward_jvp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_forward_jvp.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _fp]
     lib.bodyfit_residuals_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.bodyfit_residual_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p]
@@ -522,6 +525,38 @@ class Problem:
         rf = 3 * self.model.n_verts if grad_cloud_row_floats is None else int(grad_cloud_row_floats)
         _check(load_library().bodyfit_forward_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_cloud_ptr, rf,
                                                          d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr, stream))
+
+    def forward_jvp(self, frame_params, beta, tan_x, tan_beta=None, want_cloud=True):
+        """Forward-mode tangents of the forward (bodyfit_forward_jvp): tan_x [F, K, 7 + 3 (nJ - 1)] (or None = 0) and tan_beta
+        ([K, nS] for a shared beta, [F, K, nS] per frame; None = 0) give (tan_joints [F, K, nJ, 3] f64, tan_cloud [F, K, V, 3]
+        f32 or None), the directional derivatives of forward()'s joints and cloud along each of the K tangents."""
+        x = _c64(frame_params); b = _c64(beta) if beta is not None else None
+        assert x.size >= self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
+        F, nS = self.n_frames, self.model.n_shape
+        tx = _c64(tan_x) if tan_x is not None else None
+        tb = _c64(tan_beta) if tan_beta is not None else None
+        assert tx is not None or tb is not None, "give tan_x or tan_beta"
+        if tx is not None:
+            assert tx.ndim == 3 and tx.shape[0] == F and tx.shape[2] == self.n_frame_params, "tan_x must be [F, K, n_frame_params]"
+            K = tx.shape[1]
+        else:
+            K = tb.shape[-2]
+        if tb is not None:
+            want = (F, K, nS) if self.beta_per_frame else (K, nS)
+            assert tb.shape == want, f"tan_beta must be {list(want)}"
+        joints = np.empty((F, K, self.model.n_joints, 3))
+        cloud = np.empty((F, K, self.model.n_verts, 3), np.float32) if want_cloud else None
+        _check(load_library().bodyfit_forward_jvp(self.h, _d(x), _d(b), K, _d(tx), _d(tb), _d(joints),
+                                                  cloud.ctypes.data_as(_fp) if cloud is not None else None))
+        return joints, cloud
+
+    def forward_jvp_device(self, d_params_ptr: int, d_beta_ptr: int | None, n_tangents: int, d_tan_params_ptr: int | None,
+                           d_tan_beta_ptr: int | None, d_tan_joints_ptr: int | None, d_tan_cloud_ptr: int | None,
+                           row_floats: int | None = None, stream: int | None = None):
+        """bodyfit_forward_jvp_device: asynchronous on `stream`, device pointers throughout."""
+        rf = 3 * self.model.n_verts if row_floats is None else int(row_floats)
+        _check(load_library().bodyfit_forward_jvp_device(self.h, d_params_ptr, d_beta_ptr, int(n_tangents), d_tan_params_ptr,
+                                                         d_tan_beta_ptr, d_tan_joints_ptr, d_tan_cloud_ptr, rf, stream))
 
     def residuals_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_residuals_ptr: int, d_comp_ptr: int | None = None,
                          keep_jacobian=False, stream: int | None = None):

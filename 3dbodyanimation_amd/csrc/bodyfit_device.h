@@ -367,6 +367,19 @@ void launch_vjp_chain(const DevModel& M, const DevProblem& P, const double* d_pa
                       const float* d_part, const double* d_H, double* d_gx, double* d_gbeta_frames, hipStream_t s);
 void launch_vjp_beta_sum(const double* d_gbeta_frames, int F, int nS, double* d_out, hipStream_t s);
 
+// forward-mode tangents of the forward, K per frame (k_forward_jvp.hip; bodyfit_forward_jvp_device)
+size_t jvp_feat_elems(int F);                // bf16 entries of one tangent tile's blend-coefficient fragments per problem
+size_t jvp_tdot_elems(int F);                // f32 entries of one tangent tile's transform tangents per problem
+size_t jvp_bbuf_elems(int F, int nVT);       // f32 entries of the primal blended rest vertices
+size_t jvp_dbuf_elems(int F, int nVT);       // f32 entries of one tangent tile's blended-vertex tangents per problem
+void launch_jvp_blend(const DevModel& M, const DevProblem& P, const MeshCoef& mc, float* d_bbuf, hipStream_t s);
+// tangents k0 .. k0 + 32 n_tiles - 1 (clipped to K); d_tdot / d_featD null: joints only
+void launch_jvp_chain(const DevModel& M, const DevProblem& P, const double* d_params, const double* d_beta, int K, int k0,
+                      int n_tiles, const double* d_tan_params, const double* d_tan_beta, int tan_beta_per_frame,
+                      double* d_tan_joints, float* d_tdot, uint16_t* d_featD, hipStream_t s);
+void launch_jvp_mesh(const DevModel& M, const DevProblem& P, const MeshCoef& mc, const uint16_t* d_featD, const float* d_tdot,
+                     const float* d_bbuf, float* d_dbuf, int K, int k0, float* d_out, long long row_floats, hipStream_t s);
+
 // vector-Jacobian product of the whole residual vector (k_residual_vjp.hip; bodyfit_residual_vjp_device)
 struct ResVjpArgs {
   int F, n_param_rows, ncols, npose, nS;

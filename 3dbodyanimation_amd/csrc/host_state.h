@@ -258,6 +258,19 @@ struct bodyfit_problem {
   float* vjp_part = nullptr;
   double* vjp_dT = nullptr;
 
+  // ---- forward JVP (k_forward_jvp.hip): buffers allocated on the problem's first JVP with a cloud tangent
+  // (bodyfit_forward_jvp_device): its own mesh operands, the primal blended vertices [F][Vp][3], and one 32-tangent tile per
+  // frame of transform tangents [F][32][24][12] f32, blend-coefficient fragments [F][14][2][64][8] bf16 and blended-vertex
+  // tangents [F][32][Vp][3] f32
+  bool jvp_alloc = false;
+  bodyfit::MeshCoef jvp_mc{};
+  double* jvp_r = nullptr;
+  double* jvp_joints = nullptr;
+  float* jvp_bbuf = nullptr;
+  float* jvp_tdot = nullptr;
+  float* jvp_dbuf = nullptr;
+  uint16_t* jvp_featD = nullptr;
+
   // ---- residual VJP (k_residual_vjp.hip): whether d_J / d_comp hold the dense Jacobian of the last sweep (a Jacobian sweep into the
   // problem's own buffers sets it; residual-only sweeps, the solves and every other writer of d_r / d_J clear it), the per-frame
   // beta partials of a shared beta and the GMM prior's transposed factor rows, both allocated on the first residual VJP

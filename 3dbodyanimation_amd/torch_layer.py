@@ -5,7 +5,9 @@
     loss(verts, joints).backward()
 
 forward is bodyfit_forward_device (the two-launch sweep: verts [F, V, 3] f32, joints [F, 24, 3] f64), backward is
-bodyfit_forward_vjp_device (HIP kernels, k_forward_vjp.hip).  Both run on torch.cuda.current_stream() without a host
+bodyfit_forward_vjp_device (HIP kernels, k_forward_vjp.hip); forward-mode AD (torch.autograd.forward_ad) and layer.jvp /
+layer.jacobian are bodyfit_forward_jvp_device (k_forward_jvp.hip: K tangents per frame at once, the dense Jacobian with the unit
+tangents).  Both run on torch.cuda.current_stream() without a host
 synchronisation.  The layer keeps one keypoint-free problem (want_mesh) per frame count.  Calls that share a frame count share
 that problem's device buffers, so interleaving them on several streams at once needs the caller's own ordering (events).
 
@@ -62,7 +64,25 @@ class _SMPLForward(torch.autograd.Function):
         ctx.n_verts = n_verts
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, beta)
+        ctx.save_for_forward(x, beta)
         return verts, joints
+
+    @staticmethod
+    def jvp(ctx, x_t, beta_t, *_):
+        # forward-mode AD (torch.autograd.forward_ad): one tangent, bodyfit_forward_jvp_device; a missing tangent is zero
+        x, beta = ctx.saved_tensors
+        F = x.shape[0]
+        n_joints = (x.shape[1] - 7) // 3 + 1
+        verts_t = torch.empty((F, ctx.n_verts, 3), dtype=torch.float32, device=x.device)
+        joints_t = torch.empty((F, n_joints, 3), dtype=torch.float64, device=x.device)
+        if x_t is not None:
+            x_t = x_t.to(torch.float64).contiguous()
+        if beta_t is not None:
+            beta_t = beta_t.to(torch.float64).contiguous()
+        ctx.prob.forward_jvp_device(x.data_ptr(), beta.data_ptr(), 1, x_t.data_ptr() if x_t is not None else None,
+                                    beta_t.data_ptr() if beta_t is not None else None, joints_t.data_ptr(),
+                                    verts_t.data_ptr(), 3 * ctx.n_verts, _stream())
+        return verts_t, joints_t
 
     @staticmethod
     @once_differentiable
@@ -118,7 +138,7 @@ class SMPLLayer(torch.nn.Module):
             self._problems[F] = p
         return p
 
-    def forward(self, x: torch.Tensor, beta: torch.Tensor):
+    def _check(self, x, beta):
         if not isinstance(x, torch.Tensor) or not isinstance(beta, torch.Tensor):
             raise TypeError("x and beta must be torch tensors")
         if not (x.is_cuda and beta.is_cuda):
@@ -133,7 +153,66 @@ class SMPLLayer(torch.nn.Module):
             raise ValueError(f"beta must be {list(want_b)}, got {list(beta.shape)}")
         if x.device.index != self.model.device or beta.device != x.device:
             raise ValueError(f"x and beta must be on cuda:{self.model.device}")
+        return F
+
+    def forward(self, x: torch.Tensor, beta: torch.Tensor):
+        F = self._check(x, beta)
         return _SMPLForward.apply(x.contiguous(), beta.contiguous(), self.problem(F), self.model.n_verts, self.model.n_joints)
+
+    def jvp(self, x: torch.Tensor, beta: torch.Tensor, tan_x: torch.Tensor | None, tan_beta: torch.Tensor | None = None):
+        """Forward-mode tangents of forward(x, beta) along K tangents at once (bodyfit_forward_jvp_device, HIP kernels in
+        k_forward_jvp.hip; nothing is recorded for autograd): tan_x [F, K, 76] f64 (None: zero) and tan_beta [K, nS], or
+        [F, K, nS] with beta_per_frame (None: zero), give (tan_verts [F, K, V, 3] f32, tan_joints [F, K, nJ, 3] f64).  The result
+        for a (frame, tangent) pair does not depend on F, K or the tangent's position, bit for bit."""
+        F = self._check(x, beta)
+        nS = self.model.n_shape
+        if tan_x is None and tan_beta is None:
+            raise ValueError("give tan_x or tan_beta")
+        for name, t in (("tan_x", tan_x), ("tan_beta", tan_beta)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch tensor")
+            if not t.is_cuda or t.device != x.device:
+                raise ValueError(f"{name} must be on cuda:{self.model.device}")
+            if t.dtype != torch.float64:
+                raise TypeError(f"{name} must be float64")
+        if tan_x is not None:
+            if tan_x.ndim != 3 or tan_x.shape[0] != F or tan_x.shape[2] != api.N_FRAME_PARAMS or tan_x.shape[1] < 1:
+                raise ValueError(f"tan_x must be [{F}, K, {api.N_FRAME_PARAMS}], got {tuple(tan_x.shape)}")
+            K = tan_x.shape[1]
+        else:
+            if tan_beta.ndim < 2 or tan_beta.shape[-2] < 1:
+                raise ValueError(f"tan_beta must be [K, {nS}] or [F, K, {nS}], got {tuple(tan_beta.shape)}")
+            K = tan_beta.shape[-2]
+        if tan_beta is not None:
+            want_tb = (F, K, nS) if self.beta_per_frame else (K, nS)
+            if tuple(tan_beta.shape) != want_tb:
+                raise ValueError(f"tan_beta must be {list(want_tb)}, got {list(tan_beta.shape)}")
+        x, beta = x.detach().contiguous(), beta.detach().contiguous()
+        tan_x = tan_x.detach().contiguous() if tan_x is not None else None
+        tan_beta = tan_beta.detach().contiguous() if tan_beta is not None else None
+        V, nJ = self.model.n_verts, self.model.n_joints
+        tan_verts = torch.empty((F, K, V, 3), dtype=torch.float32, device=x.device)
+        tan_joints = torch.empty((F, K, nJ, 3), dtype=torch.float64, device=x.device)
+        self.problem(F).forward_jvp_device(x.data_ptr(), beta.data_ptr(), K, tan_x.data_ptr() if tan_x is not None else None,
+                                           tan_beta.data_ptr() if tan_beta is not None else None, tan_joints.data_ptr(),
+                                           tan_verts.data_ptr(), 3 * V, _stream())
+        return tan_verts, tan_joints
+
+    def jacobian(self, x: torch.Tensor, beta: torch.Tensor):
+        """The dense Jacobian of forward(x, beta): jvp with the P = 76 + nS unit tangents.  (Jv [F, P, V, 3] f32,
+        Jj [F, P, nJ, 3] f64); slice p < 76 is the derivative w.r.t. frame parameter p of that frame, slice 76 + i the
+        derivative w.r.t. beta_i (of that frame's beta with beta_per_frame, of the shared beta otherwise)."""
+        F = self._check(x, beta)
+        nP, nS = api.N_FRAME_PARAMS, self.model.n_shape
+        P = nP + nS
+        eye = torch.eye(P, dtype=torch.float64, device=x.device)
+        tan_x = eye[:, :nP].expand(F, P, nP).contiguous()
+        tan_beta = None
+        if nS > 0:
+            tan_beta = eye[:, nP:].expand(F, P, nS).contiguous() if self.beta_per_frame else eye[:, nP:].contiguous()
+        return self.jvp(x, beta, tan_x, tan_beta)
 
 
 def huber_rho(delta: float, s: torch.Tensor) -> torch.Tensor:

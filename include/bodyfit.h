@@ -279,6 +279,33 @@ int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params,
 int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* grad_cloud,
                         const double* grad_joints, double* grad_frame_params, double* grad_beta);
 
+/* Forward-mode tangents (Jacobian-vector products) of that forward, n_tangents = K per frame at once: given
+ *   d_tan_params [F][K][76] f64 = the tangents of the frame parameters (order [s, rootAA, rootT, jointAA[1..]]; NULL: 0; a
+ *                temporal_halo problem's extra parameter row is read past and has no tangent),
+ *   d_tan_beta   [K][nS] f64 when beta is shared, [F][K][nS] when beta_per_frame (NULL: 0; ignored with n_cols = 76),
+ * writes the directional derivatives of exactly what bodyfit_forward_device computes,
+ *   d_tan_joints [F][K][nJ][3] f64 or NULL,   d_tan_cloud [F][K][row_floats] f32 (row_floats >= 3 V; needs want_mesh) or NULL,
+ * under the problem's use_shape / pose_blend / beta_per_frame and its fixed R0 (without pose_blend the pose features carry no
+ * tangent, without use_shape beta carries none).  With the 76 + nS unit tangents the outputs are the dense Jacobian.
+ * Tolerances (against central differences of the f64 forward): joints <= 1e-7, cloud <= 1e-4 of the largest entry of that
+ * (frame, tangent)'s tangent; the chain is f64, the blend tangent runs on the matrix pipe like the forward's blend (bf16 hi/lo
+ * split, f32 accumulation) and the skinning tangent is f32.
+ * Deterministic: no atomics, fixed summation orders; the outputs of (frame, tangent) depend on that frame's parameters and that
+ * tangent only (bit-identical whatever F and K and wherever the tangent sits); a zero tangent gives exactly 0.
+ * Memory: buffers of its own, allocated on the problem's first JVP with d_tan_cloud and freed with the problem (about 2.8 MB per
+ * frame whatever K: one tile of 32 tangents per frame, the tiles run one after the other); the sweep buffers, the dense-Jacobian
+ * flag and the VJP's buffers are left alone.  Without d_tan_cloud only the f64 chain kernel runs and nothing is allocated
+ * (problems without want_mesh and models with n_joints != 24 included).
+ * Asynchronous on `stream`, ordered like bodyfit_evaluate_device.
+ * BODYFIT_ERR_INVALID: NULL problem / parameters, n_tangents < 1, both outputs NULL, d_tan_cloud without want_mesh or with
+ * row_floats < 3 V.                                                                                                       */
+int bodyfit_forward_jvp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, int n_tangents,
+                               const double* d_tan_params, const double* d_tan_beta, double* d_tan_joints, float* d_tan_cloud,
+                               long long row_floats, void* stream);
+/* Host-pointer form of bodyfit_forward_jvp_device (same shapes, tan_cloud rows of 3 V floats), synchronous. */
+int bodyfit_forward_jvp(bodyfit_problem* p, const double* frame_params, const double* beta, int n_tangents,
+                        const double* tan_params, const double* tan_beta, double* tan_joints, float* tan_cloud);
+
 /* ---- the fitting objective as a differentiable function of (frame_params, beta) ----------------------------------------
  * Residual vector into caller memory: the sweep at (frame_params, beta) (without the mesh), then an asynchronous copy of the
  * problem's residuals [total_rows] (bodyfit_problem_layout row order) to d_residuals and, if d_gmm_comp [F] is not NULL, of the
