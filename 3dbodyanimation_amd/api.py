@@ -237,6 +237,9 @@ def load_library():
     lib.bodyfit_closest_surface_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int,
                                                        C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+    lib.bodyfit_surface_gram_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong,
+                                                C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_writeback_batch.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _fp, _dp]
     lib.bodyfit_evaluate_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(_dp), _dp, C.POINTER(_dp)]
     _u8p = C.POINTER(C.c_uint8)
@@ -779,6 +782,18 @@ class Surface:
         _check(load_library().bodyfit_closest_surface_vjp_device(self.h, C.byref(query), d_verts_ptr, int(verts_frame_stride),
                                                                  int(n_frames), int(n_query_total), d_index_ptr, d_bary_ptr,
                                                                  d_grad_dist2_ptr, d_grad_query_ptr, d_grad_verts_ptr, stream))
+
+    def gram_device(self, query: PointSet, n_frames: int, n_query_total: int, d_index_ptr: int, d_bary_ptr: int,
+                    d_weight_ptr: int | None, d_direction_ptr: int | None, d_jac_ptr: int, n_tangents: int, row_floats: int,
+                    jac_frame_stride: int, d_rhs_ptr: int | None, rhs_frame_stride: int, d_H_ptr: int, d_g_ptr: int | None,
+                    stream: int | None = None):
+        """bodyfit_surface_gram_device: the per-frame normal equations H [F, P, P] f64 = J^T W J (and g [F, P] f64 = J^T rhs) of
+        the scan rows at the fixed (index, bary), from the dense vertex Jacobian [F, P, row_floats] f32; weight [N] f32 and
+        direction [N, 3] f32 (point-to-plane) are optional, asynchronous on `stream`."""
+        _check(load_library().bodyfit_surface_gram_device(self.h, C.byref(query), int(n_frames), int(n_query_total), d_index_ptr,
+                                                          d_bary_ptr, d_weight_ptr, d_direction_ptr, d_jac_ptr, int(n_tangents),
+                                                          int(row_floats), int(jac_frame_stride), d_rhs_ptr,
+                                                          int(rhs_frame_stride), d_H_ptr, d_g_ptr, stream))
 
     def close(self):
         if getattr(self, "h", None):

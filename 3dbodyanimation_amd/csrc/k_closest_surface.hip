@@ -50,7 +50,7 @@
 #include "bodyfit_device.h"
 #include "host_state.h"
 
-#include "closest_group_inl.h"
+#include "surface_handle.h"
 
 namespace bodyfit {
 
@@ -434,22 +434,7 @@ __global__ __launch_bounds__(256) void k_cs_vjp_verts(const SurfVjpArgs a) {
 
 }  // namespace bodyfit
 
-struct bodyfit_surface {
-  bodyfit::ClosestWorkspace w;
-  int n_verts = 0, n_faces = 0;
-  int* d_faces = nullptr;      // [n_faces][3]
-  int* d_csr_off = nullptr;    // [n_verts + 1]
-  int* d_csr_fc = nullptr;     // [3 n_faces]
-  char* rec = nullptr;         // the prepared records of the last search
-  size_t rec_bytes = 0;
-  char* acc = nullptr;         // per-face corner sums of a backward
-  size_t acc_bytes = 0;
-};
-
 namespace {
-
-// the faces as a uniform "reference set" of n_faces rows per frame: what the grouping counts rows of
-bodyfit_pointset face_rows(const bodyfit_surface* s) { return bodyfit_pointset{nullptr, nullptr, s->n_faces, 3LL * s->n_faces}; }
 
 int check_surface_call(const char* fn, const bodyfit_surface* s, const bodyfit_pointset* query, const float* d_verts,
                        long long stride, int n_frames, long long* nq) {
@@ -508,7 +493,7 @@ int bodyfit_surface_create(int device, int n_verts, int n_faces, const int32_t* 
 void bodyfit_surface_destroy(bodyfit_surface* s) {
   if (!s) return;
   (void)hipSetDevice(s->w.device);
-  for (void* p : {(void*)s->d_faces, (void*)s->d_csr_off, (void*)s->d_csr_fc, (void*)s->rec, (void*)s->acc})
+  for (void* p : {(void*)s->d_faces, (void*)s->d_csr_off, (void*)s->d_csr_fc, (void*)s->rec, (void*)s->acc, (void*)s->gram})
     if (p) (void)hipFree(p);
   bodyfit::release_workspace(&s->w);
   delete s;

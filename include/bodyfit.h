@@ -494,6 +494,55 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
                                        long long verts_frame_stride, int n_frames, long long n_query_total, const int32_t* d_index,
                                        const float* d_bary, const float* d_grad_dist2, float* d_grad_query, float* d_grad_verts,
                                        void* stream);
+/* The Gauss-Newton NORMAL EQUATIONS of a scan term at a fixed correspondence, per frame, without ever holding a per-row Jacobian
+ * (k_surface_gram.hip).  Row i of frame f (packed like d_dist2) carries d_index[i] = t_i, d_bary[i] = b_i, optionally a weight
+ * w_i (d_weight [N] f32; NULL: 1) and a unit direction d_i (d_direction [N][3] f32; NULL: point-to-point).  d_jac is the dense
+ * Jacobian of the frame's vertices in the layout of bodyfit_forward_jvp_device's d_tan_cloud: [F][P][row_floats] f32, P =
+ * n_tangents, tangent p of frame f at d_jac + f jac_frame_stride + p row_floats, its first 3 V floats J_f[p][v][0..2] (row_floats
+ * >= 3 V; what lies behind the 3 V floats of a row is never read and may hold anything, NaN included).
+ * CONTRACT.  With A_i[:, p] = sum_a b_ia J_f[p][faces[t_i][a]][0..2], the 3-vector by which tangent p moves the row's surface point,
+ *   d_H[f][p][q] = sum_i w_i (A_i[:, p] . A_i[:, q])                        without d_direction (point-to-point),
+ *   d_H[f][p][q] = sum_i w_i (d_i . A_i[:, p]) (d_i . A_i[:, q])            with it (point-to-plane),
+ * over the rows i of frame f with 0 <= t_i < n_faces, [F][P][P] f64, the full symmetric panel; and, with d_rhs [F][V][3] f32
+ * (rhs_frame_stride floats between frames, >= 3 V), d_g[f][p] = sum_v J_f[p][v] . rhs_f[v], [F][P] f64 (d_g NULL: not computed;
+ * d_g needs d_rhs).  These are J^T W J and J^T rhs of the cost 1/2 sum_i w_i |r_i|^2 when rhs = dcost/dverts.  A row with t_i = -1
+ * or out of range, or with w_i = 0, contributes nothing; a frame without rows gets exact zeros.
+ * How: sum_i w_i A_i^T D_i A_i = J^T W J with W the 3 V x 3 V matrix of the per-face moments M_t[a][c] = sum_{i -> t} w_i b_ia b_ic
+ * D_i (D_i = I or d_i d_i^T), non-zero on the mesh's vertices and edges only: moments per face, the sparse mix Y = W J, and the
+ * dense contraction H = J . Y^T on the matrix pipe (bf16 hi / lo split of both operands, hi.hi + hi.lo + lo.hi, f32
+ * accumulation over slices of 256 floats of the contracted index, the slices' partial panels summed in f64).
+ * PRECISION.  With H* the exact value of the formula above on the f32 inputs, and H^ the same sum with every factor replaced by
+ * its absolute value and the dot products expanded, H^[p][q] = sum_i |w_i| sum_{a,c,x,y} |b_ia b_ic D_i[x][y] J[p][v_a][x] J[q][v_c][y]|
+ * (D_i[x][y] = [x = y] or d_ix d_iy),
+ *   |d_H - H*| <= eps H^ elementwise, eps = 2^-12;      |d_g - g*| <= eps_g g^, eps_g = 2^-32, g^ = sum_k |J[p][k] rhs[k]|.
+ * Derivation, in units of u = 2^-24.  Moments: products and sums in f64 (each term carries at most 6 roundings of 2^-53, a sum of
+ * n terms n more: below 2^-28 u for any n < 2^21), rounded once to f32: 1.  Y: f64 sums of f32 x f32 products (exact), at most
+ * 2^-20 u, rounded once to f32: 1.  The split: x = hi + lo + r with hi the bf16 nearest x (8 significant bits: |x - hi| <= 2^-8
+ * |x|) and lo the bf16 nearest x - hi, so |lo| <= 2^-8 |x| and |r| <= 2^-16 |x|; the three products that are formed miss lo.lo
+ * and the terms in r: 2^-16 + 2 x 2^-16 (1 + 2^-7) < 3.02 x 2^-16 = 773.2 of a product J Y, stated as 776.  bf16 x bf16 is exact
+ * in f32.  The f32 accumulation of one partial panel entry is a chain of 3 x 256 terms whose absolute values sum to at most
+ * (1 + 2^-6) |J||Y|; with at most 2 per addition (the matrix pipe's sums are not promised to round to nearest) that is
+ * 2 x 768 x 1.016 = 1561.  The f64 fold of the partial panels: 2^-29 per slice, nothing.  Together 1 + 1 + 776 + 1561 = 2339
+ * < 4096 = 2^-12 / u, first-order terms only; the second-order ones are below 1.  (Measured on random inputs: 2e-5 H^ at the
+ * worst, the split's share.)  g: products of two f32 are exact in f64, the sum of n = 3 V terms carries n 2^-53, stated as 2^-32
+ * (n < 2^21).
+ * DETERMINISM.  H is exactly symmetric (the triangle p >= q is computed, the other is its copy).  No float atomics; per face the
+ * rows in ascending order under the 64-partial rule of bodyfit_closest_surface_vjp_device, then fixed orders over a vertex's
+ * incident corners, the contracted index and the slices: a frame's panel depends on that frame only, bit-identical whatever
+ * n_frames, from run to run, and whether the grouping was kept or rebuilt.
+ * The grouping by face is taken from the handle when d_index is the output of one of its last four prepare_vjp searches over the
+ * same set and counts, else built inside the call, as for bodyfit_closest_surface_vjp_device (query->d_xyz is not read, but must
+ * not be NULL).  The vertex -> corner table is the handle's, built in bodyfit_surface_create.  Workspace: the moments, Y and the
+ * partial panels of SIXTEEN frames at a time (the groups follow one another on the stream): per frame of a group
+ * P 3 V 4 bytes of Y, 24 (144 with directions) bytes per face and 4 KiB per (tile pair, slice), 11 MB at SMPL size with
+ * P = 86, whatever n_frames; growing it synchronises the device once, as for the searches.  Asynchronous on `stream`,
+ * ordered like the other calls on the handle.  n_frames == 0: a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / set /
+ * d_index / d_bary / d_jac / d_H, n_tangents < 1 or > 4096, row_floats < 3 V, jac_frame_stride < n_tangents row_floats,
+ * rhs_frame_stride < 3 V, d_g without d_rhs, negative counts, a (n_tangents, V) whose partial panels pass 2^31 bytes per frame. */
+int bodyfit_surface_gram_device(bodyfit_surface* s, const bodyfit_pointset* query, int n_frames, long long n_query_total,
+                                const int32_t* d_index, const float* d_bary, const float* d_weight, const float* d_direction,
+                                const float* d_jac, int n_tangents, long long row_floats, long long jac_frame_stride,
+                                const float* d_rhs, long long rhs_frame_stride, double* d_H, double* d_g, void* stream);
 
 /* The post-solve write-back of a whole solve on the device: for every frame
  *   r[0] <- R(rootAA) r[0]  (left-multiplied, so it compounds over repeated solves),  p <- rootT,
