@@ -255,6 +255,14 @@ def load_library():
                                            C.c_int]
     lib.bodyfit_overlay_drawlist.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), _i32p, _i32p, _i32p]
     lib.bodyfit_overlay_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    lib.bodyfit_raster_create.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    lib.bodyfit_raster_destroy.argtypes = [C.c_void_p]
+    lib.bodyfit_raster_destroy.restype = None
+    lib.bodyfit_raster_render_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                                 C.c_double, C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_visibility_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_last_bins.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     _lib = lib
     return lib
 
@@ -861,6 +869,64 @@ class Overlay:
     def close(self):
         if getattr(self, "h", None):
             load_library().bodyfit_overlay_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Raster:
+    """Depth and face-id render of the posed mesh on the device, and face / vertex visibility from a face-id image
+    (bodyfit_raster_*, csrc/k_raster.hip; the definition and its contract: include/bodyfit.h).  The handle holds one topology
+    (faces: int32 [n_faces, 3] with ids in [0, n_verts)), one image size and the workspace; calls on one handle must be
+    ordered (one stream, or events)."""
+
+    def __init__(self, device: int, n_verts: int, faces, width: int, height: int):
+        f = np.asarray(faces)
+        if f.dtype.kind not in "iu":
+            raise TypeError("faces must be an integer array")
+        if f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError(f"faces must be [n_faces, 3], got {f.shape}")
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        h = C.c_void_p()
+        _check(load_library().bodyfit_raster_create(int(device), int(n_verts), int(f.shape[0]),
+                                                    f.ctypes.data_as(C.POINTER(C.c_int32)), int(width), int(height),
+                                                    C.byref(h)))
+        self.h = h
+        self.device = device
+        self.n_verts, self.n_faces = int(n_verts), int(f.shape[0])
+        self.width, self.height = int(width), int(height)
+
+    def render_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, intr, d_depth_ptr: int, d_face_ptr: int,
+                      d_bary_ptr: int | None = None, z_near: float = 0.1, cull_backfaces: bool = False,
+                      stream: int | None = None):
+        """bodyfit_raster_render_device: depth [F, H, W] f32 (+inf where empty), face [F, H, W] int32 (-1 where empty) and,
+        unless None, bary [F, H, W, 3] f32 of the vertices [F, n_verts, 3] f32 at verts_frame_stride floats between frames,
+        intr = (fx, fy, cx, cy); asynchronous on `stream` but for one 8-byte read-back that sizes the tile lists."""
+        _check(load_library().bodyfit_raster_render_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                           float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
+                                                           float(z_near), int(bool(cull_backfaces)), d_depth_ptr, d_face_ptr,
+                                                           d_bary_ptr, stream))
+
+    def visibility_device(self, d_face_ptr: int, n_frames: int, d_face_visible_ptr: int | None,
+                          d_vert_visible_ptr: int | None, stream: int | None = None):
+        """bodyfit_raster_visibility_device: u8 [F, n_faces] (the face owns a pixel) and u8 [F, n_verts] (a corner of such a
+        face) from a face-id image [F, H, W] int32; either output may be None; asynchronous on `stream`."""
+        _check(load_library().bodyfit_raster_visibility_device(self.h, d_face_ptr, int(n_frames), d_face_visible_ptr,
+                                                               d_vert_visible_ptr, stream))
+
+    def last_bins(self):
+        """(face, tile) pairs binned by the latest render, and its longest tile list"""
+        n, longest = C.c_longlong(0), C.c_int(0)
+        _check(load_library().bodyfit_raster_last_bins(self.h, C.byref(n), C.byref(longest)))
+        return int(n.value), int(longest.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().bodyfit_raster_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -48,6 +48,14 @@ The second-order side of the scan terms: per frame the Gauss-Newton normal equat
 k_surface_gram.hip: per-face moments, a sparse mix and one dense contraction on the matrix pipe; no per-point Jacobian row, and
 the dense vertex Jacobian only frame_chunk frames at a time).  A keypoint + prior + scan Levenberg-Marquardt step adds these
 panels to its own and solves with torch.linalg.solve.
+
+    depth, face, bary = render_depth(verts, faces, intr, (H, W))        # what the camera sees of the posed mesh (no gradient)
+    vis = visible_vertices(verts, faces, intr, (H, W))                  # bool [F, V]
+    term = DepthMapTerm(depth_map, intr, faces, trunc=0.1, min_cos=0.2) # an RGB-D frame: both directions, the second one gated
+
+render_depth is bodyfit_raster_render_device (k_raster.hip: a z-buffer over faces binned to screen tiles, decided in f64),
+visible_vertices adds bodyfit_raster_visibility_device.  DepthMapTerm back-projects a depth map once, matches its points to
+sensor-facing triangles (SurfaceTerm with the directions towards the sensor) and pulls only the VISIBLE vertices to the points.
 """
 from __future__ import annotations
 
@@ -567,21 +575,26 @@ def _surface_handle(device_index: int, n_verts: int, faces):
         if faces.device != device_index or faces.n_verts != n_verts:
             raise ValueError(f"this Surface is for cuda:{faces.device} and {faces.n_verts} vertices, got cuda:{device_index} and {n_verts}")
         return faces
+    return _topology_handle(_surface_handles, device_index, n_verts, faces, (),
+                            lambda f: api.Surface(device_index, n_verts, f))
+
+
+def _topology_handle(cache: dict, device_index: int, n_verts: int, faces, extra: tuple, make):
+    """the handle make(faces) of (device, topology, extra) in `cache`, keyed on the faces' content as _surface_handle describes"""
     f = _host_faces(faces)
     raw = f.tobytes()
-    key = (device_index, int(n_verts), f.shape[0], hash(raw))
-    hit = _surface_handles.pop(key, None)
+    key = (device_index, int(n_verts), f.shape[0], hash(raw)) + extra
+    hit = cache.pop(key, None)
     if hit is not None and hit[0] != raw:        # (two topologies under one hash: the kept one makes way)
         hit = None
     if hit is None:
         if f.size and (int(f.min()) < 0 or int(f.max()) >= n_verts):
             raise ValueError(f"faces holds an id outside [0, {n_verts})")
-        hit = (raw, api.Surface(device_index, n_verts, f))
-    _surface_handles[key] = hit                     # (most recently used last)
-    h = hit[1]
-    while len(_surface_handles) > _SURFACE_CACHE:
-        _surface_handles.pop(next(iter(_surface_handles)))
-    return h
+        hit = (raw, make(f))
+    cache[key] = hit                                # (most recently used last)
+    while len(cache) > _SURFACE_CACHE:
+        cache.pop(next(iter(cache)))
+    return hit[1]
 
 
 class _ClosestSurface(torch.autograd.Function):
@@ -793,6 +806,125 @@ class SurfaceTerm(torch.nn.Module):
         job = _GramJob(handle, self.points, self.offset, _host_offset(self), index, bary, keep.to(torch.float32),
                        d.to(torch.float32).contiguous())
         return cost, rhs, [job]
+
+
+# ---- depth render, visibility and the depth-map term ------------------------------------------------------------------------------
+_raster_handles: dict[tuple, tuple] = {}   # (device, V, n_faces, content hash, H, W) -> (the faces' bytes, api.Raster)
+
+
+def _raster_handle(device_index: int, n_verts: int, faces, size):
+    """The api.Raster of (device, topology, image size), kept like _surface_handle's: keyed on the faces' content, the last
+    _SURFACE_CACHE in use."""
+    H, W = int(size[0]), int(size[1])
+    return _topology_handle(_raster_handles, device_index, n_verts, faces, (H, W),
+                            lambda f: api.Raster(device_index, n_verts, f, W, H))
+
+
+def _render(verts, faces, intr, size, z_near, cull_backfaces, want_bary):
+    if not isinstance(verts, torch.Tensor) or verts.dtype != torch.float32 or not verts.is_cuda:
+        raise TypeError("verts must be a float32 tensor on the GPU")
+    if verts.ndim != 3 or verts.shape[2] != 3:
+        raise ValueError(f"verts must be [F, V, 3], got {tuple(verts.shape)}")
+    if len(intr) != 4 or len(size) != 2:
+        raise ValueError("intr is (fx, fy, cx, cy), size is (height, width)")
+    v, vs, F, _ = _point_set("verts", verts.detach(), None)
+    H, W = int(size[0]), int(size[1])
+    handle = _raster_handle(v.device.index, v.shape[1], faces, (H, W))
+    depth = torch.empty((F, H, W), dtype=torch.float32, device=v.device)
+    face = torch.empty((F, H, W), dtype=torch.int32, device=v.device)
+    bary = torch.empty((F, H, W, 3), dtype=torch.float32, device=v.device) if want_bary else None
+    with torch.cuda.device(v.device):
+        handle.render_device(v.data_ptr(), vs.frame_stride, F, [float(a) for a in intr], depth.data_ptr(), face.data_ptr(),
+                             bary.data_ptr() if want_bary else None, z_near=float(z_near), cull_backfaces=cull_backfaces,
+                             stream=_stream())
+    return handle, depth, face, bary
+
+
+def render_depth(verts: torch.Tensor, faces, intr, size, z_near: float = 0.1, cull_backfaces: bool = False):
+    """What the camera intr = (fx, fy, cx, cy) sees of the posed meshes verts [F, V, 3] f32 (GPU; a view with a frame stride of its
+    own is used in place) with the triangles faces (int32 [n_faces, 3], host array or tensor), in an image of size = (height,
+    width): (depth [F, H, W] f32, +inf where empty; face [F, H, W] int32, -1 where empty; bary [F, H, W, 3] f32, the
+    screen-space barycentric weights of the pixel in that face, 0 where empty).  Pixel (i, j) is the ray through (u, v) = (j, i)
+    in the convention of synth.project; a face with a corner in front of z_near is dropped whole; cull_backfaces keeps only
+    faces whose normal, in the orientation of faces, points to the camera.  The z-buffer, its tie rule and its error bounds are
+    those of bodyfit_raster_render_device (include/bodyfit.h, k_raster.hip).
+
+    NOT differentiable: the outputs carry no gradient, whatever verts requires (the gradient of the rendered depth at the fixed
+    (face, ray) is a follow-up, DESIGN section 8).  Runs on torch.cuda.current_stream(), with one 8-byte read-back per call;
+    the handle of (device, V, faces, size) is kept between calls, and calls that share one share its workspace."""
+    _, depth, face, bary = _render(verts, faces, intr, size, z_near, cull_backfaces, True)
+    return depth, face, bary
+
+
+def visible_vertices(verts: torch.Tensor, faces, intr, size, z_near: float = 0.1, cull_backfaces: bool = False):
+    """bool [F, V]: the vertices that are a corner of a face that owns at least one pixel of render_depth(verts, faces, intr,
+    size, ...) (bodyfit_raster_visibility_device on the rendered face ids).  No gradient."""
+    handle, _, face, _ = _render(verts, faces, intr, size, z_near, cull_backfaces, False)
+    F, V = verts.shape[0], verts.shape[1]
+    vis = torch.empty((F, V), dtype=torch.uint8, device=face.device)
+    with torch.cuda.device(face.device):
+        handle.visibility_device(face.data_ptr(), F, None, vis.data_ptr(), _stream())
+    return vis.bool()
+
+
+class DepthMapTerm(torch.nn.Module):
+    """The data term of a single-view depth map, both directions, from terms that are already differentiable.
+
+    depth: [F, H, W] f32 on the GPU, metres along the optical axis; a pixel that is not finite or not > 0 holds nothing.  The
+    constructor back-projects the valid pixels through intr = (fx, fy, cx, cy) (pixel (i, j) at (u, v) = (j, i)) into a ragged
+    point set and forms their unit directions towards the sensor, once.  term(verts), verts [F, V, 3] f32, returns the f64 cost
+      data -> model: SurfaceTerm(points, offset, faces, trunc, normals=directions, min_cos)(verts): a depth pixel is matched to the
+                     closest point of a triangle that faces the sensor (n . direction >= min_cos);
+      model -> data (model_to_data): sum over the VISIBLE vertices of rho(squared distance to the closest back-projected point of
+                     the frame), rho(s) = min(s, trunc^2).  Visibility is rendered from verts.detach() at the depth map's size
+                     (visible_vertices, z_near): the back of the body and what a limb hides are not pulled to a scan that cannot
+                     contain them, which PointCloudTerm(bidirectional=True) does.
+    A frame without a valid pixel, or without a visible vertex, contributes 0 to the direction that lacks it.  Gradients are
+    those of closest_surface and closest_points at the fixed correspondence; visibility is piecewise constant and carries none.
+    The mask gather sizes its result on the host: one synchronisation per evaluation, beside the render's own read-back."""
+
+    def __init__(self, depth: torch.Tensor, intr, faces, trunc: float | None = None, min_cos: float = 0.0,
+                 z_near: float = 0.1, model_to_data: bool = True):
+        super().__init__()
+        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or not depth.is_cuda or depth.ndim != 3:
+            raise TypeError("depth must be a float32 tensor [F, H, W] on the GPU")
+        if len(intr) != 4:
+            raise ValueError("intr is (fx, fy, cx, cy)")
+        if not z_near > 0.0:
+            raise ValueError("z_near must be positive")
+        depth = depth.detach()
+        F, H, W = depth.shape
+        fx, fy, cx, cy = (float(a) for a in intr)
+        valid = torch.isfinite(depth) & (depth > 0)
+        f, i, j = torch.nonzero(valid, as_tuple=True)          # frame-major, then row-major: the packed order of a ragged set
+        z = depth[f, i, j].double()
+        p = torch.stack(((j.double() - cx) / fx * z, (i.double() - cy) / fy * z, z), dim=1)
+        toward = -p / p.norm(dim=1, keepdim=True)
+        offset = torch.zeros(F + 1, dtype=torch.int32, device=depth.device)
+        offset[1:] = valid.reshape(F, -1).sum(dim=1).cumsum(0).to(torch.int32)
+        self.intr, self.size, self.z_near = (fx, fy, cx, cy), (int(H), int(W)), float(z_near)
+        self.model_to_data = bool(model_to_data)
+        self.surface = SurfaceTerm(p.to(torch.float32).contiguous(), offset, faces, trunc=trunc,
+                                   normals=toward.to(torch.float32).contiguous(), min_cos=min_cos)
+
+    @property
+    def points(self):
+        return self.surface.points
+
+    @property
+    def offset(self):
+        return self.surface.offset
+
+    def forward(self, verts: torch.Tensor) -> torch.Tensor:
+        cost = self.surface(verts)
+        if self.model_to_data:
+            vis = visible_vertices(verts, self.surface.faces, self.intr, self.size, z_near=self.z_near)
+            query = verts[vis]                                   # [n_visible, 3], frame after frame
+            q_offset = torch.zeros(vis.shape[0] + 1, dtype=torch.int32, device=verts.device)
+            q_offset[1:] = vis.sum(dim=1).cumsum(0).to(torch.int32)
+            cost = cost + _rho_sum(*closest_points(query, self.points, query_offset=q_offset, ref_offset=self.offset),
+                                   self.surface.trunc)
+        return cost
 
 
 # ---- Gauss-Newton normal equations of the scan terms ----------------------------------------------------------------------------

@@ -713,6 +713,83 @@ int bodyfit_overlay_drawlist(bodyfit_overlay* ov, int frame, int* n_items, int32
  * [0] faces, [1] sort + rank, [2] binning (count, scan, fill), [3] tiles                                  */
 int bodyfit_overlay_last_timing(bodyfit_overlay* ov, float ms[4]);
 
+/* ---- depth render and visibility (k_raster.hip): what one calibrated camera sees of the posed mesh ---------------------------
+ * A bodyfit_raster holds one topology (faces: host int32 [n_faces][3], ids in [0, n_verts), else BODYFIT_ERR_INVALID; n_faces =
+ * 0 is accepted) and one image size (1 .. 16384 each way) on one device, and the workspace of its calls, which grows on demand
+ * (96 bytes per (frame, face), 12 per (frame, tile of 32 x 8 pixels), 4 per (face, tile) pair).                               */
+typedef struct bodyfit_raster bodyfit_raster;
+int bodyfit_raster_create(int device, int n_verts, int n_faces, const int32_t* faces, int width, int height,
+                          bodyfit_raster** out);
+void bodyfit_raster_destroy(bodyfit_raster* r);
+/* The z-buffer of n_frames posed meshes (d_verts [F][n_verts][3] f32, verts_frame_stride floats between frames, >= 3 n_verts:
+ * bodyfit_device_views.cloud is used in place): per frame d_depth f32 [H][W] (+inf where empty), d_face int32 [H][W] (-1 where
+ * empty) and, unless NULL, d_bary f32 [H][W][3] (0 where empty), dense, frame after frame.  Every pixel of every frame is
+ * written: nothing depends on what the outputs held.
+ * DEFINITION, evaluated exactly from the f32 vertices and the f64 intrinsics (fx, fy > 0).  Corner a of a face projects to
+ * (u_a, v_a) = (fx X_a / Z_a + cx, fy Y_a / Z_a + cy), the convention of the keypoint residual; pixel (row i, column j) is the
+ * sample s = (j, i).  With A = (p1 - p0) x (p2 - p0) the doubled signed area of the projected face (x: the 2-D cross product),
+ * face t is DRAWN iff its nine coordinates are finite, every Z_a >= z_near, and A != 0; with cull_backfaces also A < 0.  A < 0 is
+ * a front face: A = fx fy (n . v0) / (Z0 Z1 Z2) with n = (v1 - v0) x (v2 - v0) the normal in the orientation of `faces`, so A < 0
+ * iff n points to the camera, the orientation (counter-clockwise seen from outside, y down) in which the overlay's backface_cull
+ * keeps a face.  (The overlay tests n_z < 0, the sign of n . v0 for a face on the optical axis; the two differ only on faces
+ * seen nearly edge-on away from the image centre, where n_z and n . v0 have different signs.)  A face with a corner in front
+ * of z_near is dropped WHOLE: there is no clipping.  The screen-space barycentrics of s are lambda_a = (p_b - s) x (p_c - s) / A
+ * (b, c the two corners after a); a drawn face covers s iff all three are >= 0 (edges inclusive); its depth there is the
+ * perspective-correct z = 1 / sum_a lambda_a / Z_a.  The pixel gets the covering face of least z, ties to the lowest face id,
+ * and that face's lambda in d_bary.
+ * CONTRACT, with u = 2^-24, k_e = 2, k_z = 2 and per face P_t = max_a max(|u_a|, |v_a|) + max(W, H) + max(|cx|, |cy|) (a bound
+ * on every corner, and on every corner - sample), Q_t = P_t^2 / |A_t|, R_t = max_a Z_a / min_a Z_a,
+ *   tau_t = k_e u (1 + 2^-22 Q_t),        c_t = 2^-19 Q_t R_t.
+ * Call a drawn face SURELY COVERING at s when min_a lambda_a >= tau_t and SURELY MISSING when min_a lambda_a < -tau_t.  Then at
+ * every pixel, with t^ the returned face and z^ the returned depth:
+ *   (a) t^ is not surely missing (and has finite corners at or behind z_near, and with cull_backfaces A <= 2^-46 P_t^2);
+ *   (b) |z^ - z(t^, s)| <= (k_z + c_t^) u z^, z(t^, s) evaluated at the lambda clamped to the triangle (negative ones to 0,
+ *       the rest rescaled to sum 1);
+ *   (c) z^ <= (1 + (k_z + c_t) u) z(t, s) for every surely covering t;
+ *   (d) the pixel is empty only if no face surely covers it;
+ *   (e) the returned weights are >= 0, within tau_t^ of the exact lambda of t^, and sum to 1 within 2 tau_t^.
+ * For a face of a body mesh in an HD image Q_t is about 2^18 and R_t about 1: tau_t = 2.1 u and c_t < 1, so (b) is 3 u z^.  The
+ * terms in Q_t are the price of a sliver: no evaluation from rounded projections can place a sample against an edge of a face
+ * whose area is lost in P_t^2.  Q_t = infinity (A = 0 to the last bit) makes (a), (c), (d) empty statements, as they must be.
+ * Derivation (k_raster.hip; eps = 2^-53 = 2^-29 u).  Everything that decides is f64.  u_a: the quotient, the product and the sum
+ * round once each, 3 eps P.  A corner - sample difference d: one more, 4 eps P, |d| <= P.  An edge function E = d1 d2 - d3 d4
+ * with the two products rounded separately (never fused: a sample exactly on an edge gives exactly 0, and the two faces of a
+ * shared edge compute E and -E): three roundings of numbers <= 2 P^2, 4 eps P^2, and four factors off by 4 eps P against
+ * partners <= P, 16: 20 eps P^2.  A, from corner differences <= 2 P known to 8 eps P: 64 + 16 = 80 eps P^2.  lambda = E (1 / A):
+ * two more roundings; for |lambda| <= 1 the error is at most 100 eps Q + 2 eps.  In units of u that is 100 x 2^-29 Q <= 2^-22 Q:
+ * the decision lambda >= 0 is right outside a band of 2^-22 Q u, and the f32 rounding of a returned weight adds at most u: tau
+ * with k_e = 1, stated as 2 for the second-order terms.  The integer bounding box in front of the evaluation (ceil / floor of
+ * the computed corners) removes only samples outside the exact triangle or within 3 eps P of its box, far inside the band.
+ * Depth: 1 / z^ = sum lambda^_a (1 / Z_a) from the computed weights (all >= 0), against the clamped exact ones at most
+ * 3 x 100 eps Q apart each: relative to the sum that is 9 x 100 eps Q R = 7.1 x 2^-22 Q R u <= c_t u; the sum's own roundings
+ * are a few eps; the reciprocal and its conversion to f32 round once each: 1 u + eps, stated as k_z = 2.  The order is decided
+ * on the f64 1 / z before that conversion, which gives (c); among equal 1 / z the lowest face id wins, whatever the order in
+ * which the tile lists were filled, so the result is bit-identical from run to run and a frame's images depend on that frame
+ * only (bit-identical whatever n_frames).  A NaN or infinite vertex only removes its faces.
+ * Shape: a face kernel prepares one 96-byte record per (frame, face); the faces are binned to 32 x 8 tiles by bounding box (a
+ * count, an allocation, a fill; integer atomics); one workgroup per (frame, tile) stages its records through LDS and keeps a
+ * pixel's (1 / z, face) in registers; plain stores.  No float atomics.
+ * Asynchronous on `stream` except for ONE 8-byte read-back that sizes the tile lists (the only host synchronisation, as in
+ * bodyfit_overlay_render_device; none when n_faces = 0) and for a call that has to grow the workspace.  Calls on one handle
+ * share the workspace: order them.  n_frames == 0: a successful no-op; n_faces == 0: every pixel empty, no face kernel runs.
+ * BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames, z_near <= 0 or NaN, fx or fy <= 0 or a non-finite
+ * intrinsic, and with frames to write: NULL d_depth / d_face, NULL d_verts (n_faces > 0), a stride below 3 n_verts, 2^31 or
+ * more (frame, face) or (frame, tile) pairs.                                                                                 */
+int bodyfit_raster_render_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                 double fx, double fy, double cx, double cy, float z_near, int cull_backfaces,
+                                 float* d_depth, int32_t* d_face, float* d_bary /* may be NULL */, void* stream);
+/* Visibility from a face-id image (d_face int32 [n_frames][H][W], as rendered; a value outside [0, n_faces) is empty):
+ * d_face_visible u8 [n_frames][n_faces], 1 iff the face owns at least one pixel of its frame, else 0; d_vert_visible u8
+ * [n_frames][n_verts], 1 iff the vertex is a corner of such a face.  Exact: integer work, no tolerance.  Either output may be
+ * NULL (both: a no-op).  Asynchronous on `stream`, no host synchronisation.  BODYFIT_ERR_INVALID: NULL handle, negative
+ * n_frames, NULL d_face with something to write.                                                                             */
+int bodyfit_raster_visibility_device(bodyfit_raster* r, const int32_t* d_face, int n_frames,
+                                     uint8_t* d_face_visible /* may be NULL */, uint8_t* d_vert_visible /* may be NULL */,
+                                     void* stream);
+/* Statistics of the handle's latest render (from its read-back; no synchronisation): the (face, tile) pairs binned, and the
+ * longest tile list.                                                                                                          */
+int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
+
 /* kernels launched by this process through the library so far (benchmarks: launches per LM iteration) */
 long bodyfit_launch_count(void);
 const char* bodyfit_last_error(void);
