@@ -237,6 +237,8 @@ def load_library():
     lib.bodyfit_closest_surface_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_longlong, C.c_int,
                                                        C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+    lib.bodyfit_surface_rows_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     lib.bodyfit_surface_gram_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong,
                                                 C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -262,6 +264,9 @@ def load_library():
                                                  C.c_double, C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_visibility_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_depth_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_last_bins.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     _lib = lib
     return lib
@@ -791,6 +796,16 @@ class Surface:
                                                                  int(n_frames), int(n_query_total), d_index_ptr, d_bary_ptr,
                                                                  d_grad_dist2_ptr, d_grad_query_ptr, d_grad_verts_ptr, stream))
 
+    def rows_vjp_device(self, rows: PointSet, n_frames: int, n_rows_total: int, d_index_ptr: int, d_bary_ptr: int,
+                        d_coef_ptr: int, d_dir_ptr: int, d_gverts_ptr: int, gverts_frame_stride: int,
+                        stream: int | None = None):
+        """bodyfit_surface_rows_vjp_device: gverts [F, n_verts, 3] f32 (gverts_frame_stride floats between frames) = sum over the
+        rows of coef_i bary_ia dir_i at corner a of face index_i; index [N] int32 (-1: nothing), bary [N, 3], coef [N], dir
+        [N, 3] f32, the rows' frame structure from `rows` (its d_xyz is not read).  Deterministic, asynchronous on `stream`."""
+        _check(load_library().bodyfit_surface_rows_vjp_device(self.h, C.byref(rows), int(n_frames), int(n_rows_total), d_index_ptr,
+                                                              d_bary_ptr, d_coef_ptr, d_dir_ptr, d_gverts_ptr,
+                                                              int(gverts_frame_stride), stream))
+
     def gram_device(self, query: PointSet, n_frames: int, n_query_total: int, d_index_ptr: int, d_bary_ptr: int,
                     d_weight_ptr: int | None, d_direction_ptr: int | None, d_jac_ptr: int, n_tangents: int, row_floats: int,
                     jac_frame_stride: int, d_rhs_ptr: int | None, rhs_frame_stride: int, d_H_ptr: int, d_g_ptr: int | None,
@@ -917,6 +932,20 @@ class Raster:
         face) from a face-id image [F, H, W] int32; either output may be None; asynchronous on `stream`."""
         _check(load_library().bodyfit_raster_visibility_device(self.h, d_face_ptr, int(n_frames), d_face_visible_ptr,
                                                                d_vert_visible_ptr, stream))
+
+    def depth_rows_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, intr, d_face_image_ptr: int,
+                          d_pixel_ptr: int | None, d_offset_ptr: int | None, n_rows: int, d_index_ptr: int,
+                          d_z_ptr: int | None = None, d_bary_ptr: int | None = None, d_dir_ptr: int | None = None,
+                          stream: int | None = None):
+        """bodyfit_raster_depth_rows_device: per row (a pixel of a frame: pixel [N] int32 linear indices with offset [F + 1]
+        int32 or None for N / F per frame; both None: every pixel, N = F H W) the face of the face-id image [F, H, W] int32
+        under it (index [N] int32, -1: void), the ray-plane depth z [N] f32 (+inf: void), the object-space barycentrics bary
+        [N, 3] f32 and the direction dir [N, 3] f32 with dz/dcorner_a = bary_a dir; the last three may be None.  Asynchronous
+        on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_depth_rows_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                               float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
+                                                               d_face_image_ptr, d_pixel_ptr, d_offset_ptr, int(n_rows),
+                                                               d_index_ptr, d_z_ptr, d_bary_ptr, d_dir_ptr, stream))
 
     def last_bins(self):
         """(face, tile) pairs binned by the latest render, and its longest tile list"""

@@ -37,6 +37,8 @@
 // chose: the wave, 64 interleaved ascending partial sums and a fixed butterfly) — the grouping of closest_group_inl.h with
 // rows = faces — then one thread per (frame, vertex) adds its incident (face, corner) entries in ascending (face, corner) order
 // through the vertex -> corner CSR the handle built from the topology.  No float atomics; every order depends on the frame alone.
+// Rows VJP (k_cs_rows_vjp_faces, k_cs_rows_vjp_verts; bodyfit_surface_rows_vjp_device): the same two stages for rows that arrive with
+// their weights, coefficient and direction (the depth rows of k_raster.hip, any point-to-plane row), summed in f64.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -430,6 +432,80 @@ __global__ __launch_bounds__(256) void k_cs_vjp_verts(const SurfVjpArgs a) {
   out[0] = gx; out[1] = gy; out[2] = gz;
 }
 
+// ---- rows VJP: gverts = sum over rows of coef_i bary_ia dir_i at corner a of face index_i ----------------------------------------
+// The surface backward's two stages with the rows given instead of derived from a residual: per (frame, face) the nine f64 sums
+// S[a][c] = sum_i coef_i b_ia m_ic over the rows that chose the face, in ascending row order (more than kHeavy: 64 interleaved
+// ascending partial sums and the same butterfly), then per (frame, vertex) the incident (face, corner) entries in ascending
+// order, rounded ONCE to f32.  The vertices are never read.
+struct RowsVjpArgs {
+  int n_faces, n_verts, F;
+  long long nr_total;               // F n_faces
+  const float* bary; const float* coef; const float* dir;
+  float* gv;                        // [F][vstride]
+  long long vstride;
+  double* acc;                      // [nr_total][9]
+  const int *cnt, *start, *sorted;
+  const int *csr_off, *csr_fc;
+};
+
+__device__ __forceinline__ void rows_add_term(const RowsVjpArgs& a, int i, double* s) {
+  const double g = (double)a.coef[i];
+  const float* b = a.bary + 3 * (size_t)i;
+  const float* m = a.dir + 3 * (size_t)i;
+  const double mx = (double)m[0], my = (double)m[1], mz = (double)m[2];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double w = g * (double)b[c];   // (exact: 48 significant bits)
+    s[3 * c] += w * mx; s[3 * c + 1] += w * my; s[3 * c + 2] += w * mz;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cs_rows_vjp_faces(const RowsVjpArgs a) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool live = row < a.nr_total;
+  int n = 0, s = 0;
+  if (live) { n = a.cnt[row]; s = a.start[row]; }
+  double acc[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+  if (live && n <= kHeavy)
+    for (int k = 0; k < n; ++k) rows_add_term(a, a.sorted[s + k], acc);
+  unsigned long long heavy = __ballot(live && n > kHeavy);
+  while (heavy) {
+    const int src = __ffsll((long long)heavy) - 1;
+    heavy &= heavy - 1;
+    const int hn = __shfl(n, src, 64), hs = __shfl(s, src, 64);
+    double part[9] = {0., 0., 0., 0., 0., 0., 0., 0., 0.};
+    for (int k = lane; k < hn; k += 64) rows_add_term(a, a.sorted[hs + k], part);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+      for (int e = 0; e < 9; ++e) part[e] += __shfl_xor(part[e], d, 64);
+    }
+    if (lane == src) {
+#pragma unroll
+      for (int e = 0; e < 9; ++e) acc[e] = part[e];
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) a.acc[9 * (size_t)row + e] = acc[e];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cs_rows_vjp_verts(const RowsVjpArgs a) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (row >= (long long)a.F * a.n_verts) return;
+  const int f = (int)(row / a.n_verts), v = (int)(row - (long long)f * a.n_verts);
+  double gx = 0., gy = 0., gz = 0.;
+  const double* acc = a.acc + 9 * (size_t)f * (size_t)a.n_faces;
+  for (int k = a.csr_off[v]; k < a.csr_off[v + 1]; ++k) {
+    const double* e = acc + 3 * (size_t)a.csr_fc[k];
+    gx += e[0]; gy += e[1]; gz += e[2];
+  }
+  float* out = a.gv + (size_t)f * (size_t)a.vstride + 3 * (size_t)v;
+  out[0] = (float)gx; out[1] = (float)gy; out[2] = (float)gz;
+}
+
 }  // namespace
 
 }  // namespace bodyfit
@@ -598,6 +674,42 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
   if (a.qblocks + fblocks) BODYFIT_LAUNCH(k_cs_vjp_faces, dim3(a.qblocks + fblocks), dim3(256), 0, st, a);
   if (a.gv)
     BODYFIT_LAUNCH(k_cs_vjp_verts, dim3((unsigned)(((long long)n_frames * s->n_verts + 255) / 256)), dim3(256), 0, st, a);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_surface_rows_vjp_device(bodyfit_surface* s, const bodyfit_pointset* rows, int n_frames, long long n_rows_total,
+                                    const int32_t* d_index, const float* d_bary, const float* d_coef, const float* d_dir,
+                                    float* d_gverts, long long gverts_frame_stride, void* stream) {
+  using namespace bodyfit;
+  const char* fn = "bodyfit_surface_rows_vjp_device";
+  if (n_frames < 0) return invalid(fn, "negative n_frames");
+  if (int rc = check_set(fn, "rows", rows, n_frames, &n_rows_total)) return rc;
+  if (!s) return invalid(fn, "null handle");
+  if (gverts_frame_stride < 3LL * s->n_verts) return invalid(fn, "gverts_frame_stride < 3 n_verts");
+  if (n_rows_total > 0 && (!d_index || !d_bary || !d_coef || !d_dir)) return invalid(fn, "d_index / d_bary / d_coef / d_dir is NULL");
+  const long long n_face_rows = (long long)n_frames * s->n_faces;
+  if (n_face_rows >= (1LL << 31) - 4096 || (long long)n_frames * s->n_verts >= (1LL << 31) - 4096)
+    return invalid(fn, "more than 2^31 faces or vertices over the frames");
+  if (n_frames == 0 || s->n_verts == 0) return BODYFIT_OK;
+  if (!d_gverts) return invalid(fn, "d_gverts is NULL");
+  HIP_TRY(hipSetDevice(s->w.device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const bodyfit_pointset fr = face_rows(s);
+  RowsVjpArgs a{};
+  a.n_faces = s->n_faces; a.n_verts = s->n_verts; a.F = n_frames; a.nr_total = n_face_rows;
+  a.bary = d_bary; a.coef = d_coef; a.dir = d_dir;
+  a.gv = d_gverts; a.vstride = gverts_frame_stride;
+  a.csr_off = s->d_csr_off; a.csr_fc = s->d_csr_fc;
+  if (n_face_rows > 0) {
+    Grouping* g = nullptr;
+    if (int rc = kept_or_built_grouping(&s->w, rows, &fr, n_frames, n_rows_total, n_face_rows, d_index, st, &g)) return rc;
+    a.cnt = g->cnt; a.start = g->start; a.sorted = g->sorted;
+    if (int rc = reserve(&s->acc, &s->acc_bytes, (size_t)n_face_rows * 72)) return rc;
+    a.acc = reinterpret_cast<double*>(s->acc);
+    BODYFIT_LAUNCH(k_cs_rows_vjp_faces, dim3((unsigned)((n_face_rows + 255) / 256)), dim3(256), 0, st, a);
+  }
+  BODYFIT_LAUNCH(k_cs_rows_vjp_verts, dim3((unsigned)(((long long)n_frames * s->n_verts + 255) / 256)), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

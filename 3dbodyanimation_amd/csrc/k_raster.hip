@@ -1,4 +1,4 @@
-// Depth and face-id render of the posed mesh, and the visibility of faces and vertices from a face-id image
+// Depth and face-id render of the posed mesh, the visibility of faces and vertices from a face-id image, and the depth rows
 // (bodyfit_raster_*, include/bodyfit.h: the definition, the contract and the derivation of its constants).
 //
 //   k_rs_faces   one thread per (frame, face): the f64 projection of the three corners, the signed area, 1 / Z per corner, the
@@ -13,6 +13,9 @@
 //                keeps (1 / z, face) in registers; the three images are written with plain stores, empty tiles included, so the
 //                outputs never depend on what they held
 //   k_rs_visible one thread per pixel of a face-id image: the constant 1 into the face's and its corners' bytes, after a clear
+//   k_rs_depth_rows one thread per depth row (a pixel of a frame): the ray through the pixel against the plane of the face the
+//                face-id image holds there: z, the object-space barycentrics and the direction m with dz/dcorner_a = beta_a m
+//                (bodyfit_raster_depth_rows_device), f64 throughout, plain stores
 //
 // Arithmetic.  The decision "does face t cover pixel s" and the depth order are taken in f64 from differences (corner - pixel),
 // never from coefficients of the whole image, so the cancellation is that of the face at the pixel; products are formed
@@ -196,6 +199,85 @@ __global__ __launch_bounds__(256) void k_rs_visible(const int* __restrict__ face
     for (int k = 0; k < 3; ++k) vert_vis[frame * nV + faces[3 * f + k]] = 1;
 }
 
+// frame of packed row `row` of a ragged row set: the largest f with offset[f] <= row (closest_group_inl.h's frame_of)
+__device__ __forceinline__ int rs_frame_of(const int* __restrict__ offset, int F, long long row) {
+  int lo = 0, hi = F;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offset[mid] <= row) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One thread per depth row: the pixel's ray against the plane of the face the face-id image holds there.  A gather of 36
+// bytes of corners per row; every operation that decides is f64 and unfused (this file's contract(off)), in the order that
+// include/bodyfit.h counts and tests/depth_rows_ref.py restates: e1, e2, n = e1 x e2, d, D = n . d, N0 = n . v0, z = N0 / D,
+// x = z d, beta_a = (n . ((v_b - x) x (v_c - x))) / (n . n), m = n / D.  Only the stores round to f32.
+__global__ __launch_bounds__(256) void k_rs_depth_rows(const float* __restrict__ verts, long long frame_stride,
+                                                       const int* __restrict__ faces, int nF, int F, int W, int H, double fx,
+                                                       double fy, double cx, double cy, const int* __restrict__ face_img,
+                                                       const int* __restrict__ pixel, const int* __restrict__ offset,
+                                                       long long per_frame, long long n_rows, int* __restrict__ index,
+                                                       float* __restrict__ z_out, float* __restrict__ bary,
+                                                       float* __restrict__ dir) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const long long ppf = (long long)W * H;
+  long long frame, pix;
+  if (pixel) {
+    frame = offset ? rs_frame_of(offset, F, row) : row / per_frame;
+    pix = pixel[row];
+  } else {
+    frame = row / ppf;
+    pix = row - frame * ppf;
+  }
+  int f = -1;
+  if (pix >= 0 && pix < ppf) f = face_img[(size_t)frame * (size_t)ppf + (size_t)pix];
+  bool ok = (unsigned)f < (unsigned)nF;     // empty (-1), not a face of this topology, or a pixel outside the image
+  double zz = 0.0, b[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0};
+  if (ok) {
+    const float* c = verts + (size_t)frame * (size_t)frame_stride;
+    double v[3][3];
+    for (int k = 0; k < 3; ++k) {
+      const size_t id = (size_t)faces[3 * f + k];
+      for (int a = 0; a < 3; ++a) {
+        const float X = c[3 * id + a];
+        if (!(X - X == 0.0f)) ok = false;   // (a NaN fails every comparison; X - X is NaN for an infinity)
+        v[k][a] = (double)X;
+      }
+    }
+    const double e1x = v[1][0] - v[0][0], e1y = v[1][1] - v[0][1], e1z = v[1][2] - v[0][2];
+    const double e2x = v[2][0] - v[0][0], e2y = v[2][1] - v[0][1], e2z = v[2][2] - v[0][2];
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const long long i = pix / W, j = pix - i * W;
+    const double dx = ((double)j - cx) / fx, dy = ((double)i - cy) / fy;
+    const double D = (nx * dx + ny * dy) + nz;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    if (!(nn > 0.0) || !(D != 0.0)) ok = false;
+    if (ok) {
+      const double N0 = (nx * v[0][0] + ny * v[0][1]) + nz * v[0][2];
+      zz = N0 / D;
+      const double x[3] = {zz * dx, zz * dy, zz};
+      const double inv_nn = 1.0 / nn;
+      for (int a = 0; a < 3; ++a) {
+        const double* vb = v[(a + 1) % 3];
+        const double* vc = v[(a + 2) % 3];
+        const double px = vb[0] - x[0], py = vb[1] - x[1], pz = vb[2] - x[2];
+        const double qx = vc[0] - x[0], qy = vc[1] - x[1], qz = vc[2] - x[2];
+        const double wx = py * qz - pz * qy, wy = pz * qx - px * qz, wz = px * qy - py * qx;
+        b[a] = ((nx * wx + ny * wy) + nz * wz) * inv_nn;
+      }
+      m[0] = nx / D; m[1] = ny / D; m[2] = nz / D;
+    }
+  }
+  index[row] = ok ? f : -1;
+  if (z_out) z_out[row] = ok ? (float)zz : std::numeric_limits<float>::infinity();
+  if (bary)
+    for (int a = 0; a < 3; ++a) bary[3 * (size_t)row + a] = ok ? (float)b[a] : 0.0f;
+  if (dir)
+    for (int a = 0; a < 3; ++a) dir[3 * (size_t)row + a] = ok ? (float)m[a] : 0.0f;
+}
+
 int rs_invalid(const char* fn, const char* what) {
   return bodyfit_internal_fail(BODYFIT_ERR_INVALID, (std::string(fn) + ": " + what).c_str());
 }
@@ -329,6 +411,35 @@ int bodyfit_raster_visibility_device(bodyfit_raster* r, const int32_t* d_face, i
   if (r->nF > 0)
     BODYFIT_LAUNCH(k_rs_visible, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_face, total, ppf, r->d_faces,
                    r->nF, r->nV, d_face_visible, d_vert_visible);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                     double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                     const int32_t* d_pixel, const int32_t* d_offset, long long n_rows, int32_t* d_index,
+                                     float* d_z, float* d_bary, float* d_dir, void* stream) {
+  const char* fn = "bodyfit_raster_depth_rows_device";
+  if (!r) return rs_invalid(fn, "handle is NULL");
+  if (n_frames < 0 || n_rows < 0) return rs_invalid(fn, "negative n_frames or n_rows");
+  if (!(fx > 0.0 && fy > 0.0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)))
+    return rs_invalid(fn, "fx and fy must be positive, and the intrinsics finite");
+  if (d_offset && !d_pixel) return rs_invalid(fn, "d_offset without d_pixel");
+  const long long ppf = (long long)r->W * r->H;
+  if (!d_pixel && n_rows != ppf * n_frames) return rs_invalid(fn, "without d_pixel n_rows must be n_frames H W");
+  if (n_rows >= (1ll << 31) - 4096) return rs_invalid(fn, "2^31 rows or more in one call");
+  if (n_rows > 0 && n_frames == 0) return rs_invalid(fn, "rows without frames");
+  if (d_pixel && !d_offset && n_frames > 0 && n_rows % n_frames != 0)
+    return rs_invalid(fn, "a uniform row set needs n_rows divisible by n_frames");
+  if (n_frames == 0 || n_rows == 0) return BODYFIT_OK;
+  if (!d_face_image || !d_index) return rs_invalid(fn, "d_face_image or d_index is NULL");
+  if (r->nF > 0 && !d_verts) return rs_invalid(fn, "d_verts is NULL");
+  if (verts_frame_stride < 3ll * r->nV) return rs_invalid(fn, "verts_frame_stride below 3 n_verts");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  BODYFIT_LAUNCH(k_rs_depth_rows, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, d_verts, verts_frame_stride,
+                 r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy, cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames,
+                 n_rows, d_index, d_z, d_bary, d_dir);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

@@ -494,6 +494,38 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
                                        long long verts_frame_stride, int n_frames, long long n_query_total, const int32_t* d_index,
                                        const float* d_bary, const float* d_grad_dist2, float* d_grad_query, float* d_grad_verts,
                                        void* stream);
+/* The VJP of "barycentric x direction" ROWS (k_cs_rows_vjp_faces, k_cs_rows_vjp_verts): row i of frame f (the rows' frame
+ * structure is that of `rows`, a point set as above of which only d_offset / n_per_frame are used; d_xyz is not read, but must
+ * not be NULL) carries d_index[i] = t_i, d_bary[i] = b_i [3] f32, d_coef[i] f32 and d_dir[i] = m_i [3] f32, and
+ *   d_gverts[f][v] = sum over the rows i of frame f and the corners a with faces[t_i][a] = v of  coef_i b_ia m_i,
+ * [F][n_verts][3] f32, gverts_frame_stride floats between frames (>= 3 n_verts; the padding is left untouched).  Every vertex of
+ * every frame is written, 0 where nothing lands; a row with t_i = -1 or out of range contributes nothing and its other entries are
+ * never read; the vertices themselves are not an argument.  This is dL/dverts of the depth rows of
+ * bodyfit_raster_depth_rows_device with coef = dL/dz, and the right-hand side of any point-to-plane row (coef = -w_i r_i, m the
+ * unit normal).
+ * Two scatter-free stages, as bodyfit_closest_surface_vjp_device: per (frame, face) the nine sums S[a][c] = sum_i coef_i b_ia m_ic
+ * over the rows that chose the face, in ascending row order, in f64 (a face more than 64 rows chose: 64 interleaved ascending
+ * partial sums, then a fixed tree); then per (frame, vertex) its incident (face, corner) sums in ascending order through the
+ * handle's vertex -> corner table, in f64, rounded ONCE to f32.  Integer atomics only inside the grouping; no float atomics.  The
+ * result is bit-identical from run to run, whatever n_frames (a frame's gradient depends on that frame's rows only), and whether
+ * the grouping by face was kept or rebuilt: it is taken from the handle when d_index is the output of one of its last four
+ * prepare_vjp searches over the same set and counts, else built inside this call.  The handle cannot see another writer: a
+ * d_index that anything but such a search wrote (the depth rows kernel, the caller) must not be a buffer whose kept grouping is
+ * still in the handle, or must have a search's invalidating write in between; a buffer no search of this handle wrote is always safe.
+ * CONTRACT, u = 2^-24: with G* the exact sum above and T the same sum of the terms' absolute values, both evaluated exactly from
+ * the f32 rows,   |d_gverts - G*| <= 2 u T   per component.
+ * The count, eps = 2^-53 = 2^-29 u: coef_i b_ia is exact in f64 (48 significant bits), its product with m_ic rounds once; a term
+ * then passes at most max(64, N / 64 + 6) additions in its face's sum, N < 2^31 rows: 2^25 + 6, and at most as many as its vertex
+ * has incident corners in the second; every addition costs eps times the absolute sum so far, at most eps T.  Together (2^25 + 8
+ * + valence) eps T = (2^-4 + 2^-29 valence) u T, and the one rounding to f32 adds u |G^| <= u (1 + 2^-3) T: below 2 u T for every
+ * vertex with fewer than 2^28 incident corners, that is for every mesh of fewer than 89 million faces whatever its shape.
+ * Workspace: 72 bytes per (frame, face), shared with the surface VJP's.  Asynchronous on `stream`, ordered like the other calls
+ * on the handle.  n_frames == 0 or n_verts == 0: a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / set / d_gverts, with rows
+ * a NULL d_index / d_bary / d_coef / d_dir or set's d_xyz, negative counts, gverts_frame_stride < 3 n_verts, 2^31 - 4096 or more
+ * rows, (frame, face) or (frame, vertex) pairs.                                                                               */
+int bodyfit_surface_rows_vjp_device(bodyfit_surface* s, const bodyfit_pointset* rows, int n_frames, long long n_rows_total,
+                                    const int32_t* d_index, const float* d_bary, const float* d_coef, const float* d_dir,
+                                    float* d_gverts, long long gverts_frame_stride, void* stream);
 /* The Gauss-Newton NORMAL EQUATIONS of a scan term at a fixed correspondence, per frame, without ever holding a per-row Jacobian
  * (k_surface_gram.hip).  Row i of frame f (packed like d_dist2) carries d_index[i] = t_i, d_bary[i] = b_i, optionally a weight
  * w_i (d_weight [N] f32; NULL: 1) and a unit direction d_i (d_direction [N][3] f32; NULL: point-to-point).  d_jac is the dense
@@ -786,6 +818,76 @@ int bodyfit_raster_render_device(bodyfit_raster* r, const float* d_verts, long l
 int bodyfit_raster_visibility_device(bodyfit_raster* r, const int32_t* d_face, int n_frames,
                                      uint8_t* d_face_visible /* may be NULL */, uint8_t* d_vert_visible /* may be NULL */,
                                      void* stream);
+/* DEPTH ROWS: the projective depth residual's rows at the correspondence a render already holds (k_rs_depth_rows, k_raster.hip).
+ * A row is a pixel of a frame; its face is what d_face_image (int32 [n_frames][H][W], as rendered by this handle's topology and
+ * size; a value outside [0, n_faces) is empty) holds there.  d_pixel int32 [N]: the linear index i W + j inside the row's frame;
+ * d_offset int32 [n_frames + 1]: the rows of frame f are offset[f] .. offset[f + 1] - 1 (offset[0] = 0, offset[n_frames] = N, the
+ * ragged convention of the closest searches), or NULL: N / n_frames rows per frame.  Both NULL: every pixel of every frame in
+ * image order, N = n_frames H W.  Outputs, packed per row: d_index int32 [N] the face or -1, d_z f32 [N], d_bary f32 [N][3],
+ * d_dir f32 [N][3]; any of the last three may be NULL.  Every row is written, whatever the outputs held.
+ * DEFINITION, from the f32 corners v0, v1, v2 of the face (order of `faces`) and the f64 intrinsics, for pixel (row i, column j):
+ *   ray d = ((j - cx) / fx, (i - cy) / fy, 1),   n = (v1 - v0) x (v2 - v0),   D = n . d,
+ *   z = (n . v0) / D          the z of the ray-plane intersection x = z d; wherever the pixel lies in the face this is the
+ *                             render's perspective-correct 1 / sum_a lambda_a / Z_a,
+ *   beta_a = n . ((v_b - x) x (v_c - x)) / (n . n)   (b, c the corners after a): the OBJECT-space barycentrics of x, sum 1; not
+ *                             the screen-space lambda of bodyfit_raster_render_device,
+ *   m = n / D                 which does not depend on the orientation of `faces`.
+ * At the fixed face dz/dv_a = beta_a m^T: the plane moves with its corners through n . (beta_a delta) only, the change of n
+ * multiplies x - p = 0 for the point p = sum beta_a v_a = x.  So a depth row is a point-to-plane row of
+ * bodyfit_surface_gram_device (weights beta on the three corners, direction m / |m|, weight w |m|^2) and its gradient a row of
+ * bodyfit_surface_rows_vjp_device (coef = dL/dz).  1 / (|m| |d|) is the cosine between the face normal and the ray.
+ * A row is VOID when its pixel index is outside [0, H W), its pixel is empty, a corner is not finite, or the f64 evaluation
+ * below gives n = 0 or D = 0 (an exact n = 0 gives it whenever the corner differences are exact in f64, that is for coordinates
+ * within 2^29 of one another: the two products of a component are then rounded from equal numbers).  A void row gets index -1,
+ * z = +inf, beta = 0, m = 0.  z may be negative (a plane met behind the camera): that is not void.  beta is returned as
+ * computed, NOT renormalised and NOT clamped: a pixel in the render's coverage band (lambda within tau_t of 0) has a slightly
+ * negative weight, and a row whose face does not contain the pixel has weights outside [0, 1].
+ * CONTRACT, with u = 2^-24, k = 2 and per non-void row x = z d exact and
+ *   P = the largest magnitude among the nine corner coordinates and the three of x,
+ *   L = the largest magnitude among the coordinate differences corner - corner and corner - x (the face's extent when the
+ *       pixel lies in it),
+ *   Q = P L / |n|,   rho = max(1, P / |x|),   c = |D| / (|n| |d|)  (the cosine above),
+ *   kappa = 2^-21 rho Q / c,        kappa_b = 2^-18 rho Q^2 / c:
+ *   |z^ - z| <= (k + kappa) u |z|,    |m^_c - m_c| <= (k + kappa) u |m|,    |beta^_a - beta_a| <= (k + kappa_b) u max(1, |beta|),
+ * |m| the Euclidean and |beta| the largest-magnitude norm (|beta| <= 1 wherever the pixel lies in the face).
+ * Q is the analogue of the render's Q_t: the face's |n| against the product of where it lies and how far it reaches.  With f32
+ * corners the squared corner coordinates themselves never enter: a difference of two f32 is formed in f64 with a rounding
+ * relative to the difference (exactly, for coordinates within 2^29 of one another), so n is lost against L^2, not P^2; P enters
+ * once through n . v0 (rho, c: a plane that passes near the camera, a grazing ray) and once through x in beta.  For a 2 cm face
+ * of a body at 3 m Q is about 300: kappa = 2^-13, kappa_b = 2^-1.5, so the three bounds are 2 u, 2 u and 2.4 u.  A row the
+ * evaluation voids although n and D are not 0 has kappa >= 2^24 (shown below): the bound it would have exceeds z itself.
+ * Derivation (eps = 2^-53 = 2^-29 u; every operation f64, products and sums separately rounded, never fused; S = L^2 / |n|,
+ * 1/3 <= S <= 2 Q because |n| <= |e1| |e2| <= 3 L^2 and L <= 2 P).  e = v_b - v_0: |e_c| <= L, off by eps L.  A component of n:
+ * two products <= L^2 (2 eps L^2), their difference <= 2 L^2 (2 eps L^2), four factors off by eps L against partners <= L
+ * (4 eps L^2): 8 eps L^2, |dn| <= 14 eps L^2 = 14 eps S |n|.  d: a difference and a quotient, 2 eps |d|.  D = (n_x d_x + n_y d_y)
+ * + n_z: |dn| |d|, 2 eps |n| |d| from d, two products and two sums of numbers <= sqrt 3 |n| |d| (7 eps): dD <= eps |n| |d| (14 S +
+ * 9).  N0 = n . v0 with |v0| <= sqrt 3 P: 24.3 eps S |n| P from dn and 5.2 eps |n| P from three products and two sums.  z = N0 / D
+ * with |N0| = |z| |D| and |D| = c |n| |d|, one more rounding:
+ *   dz / |z| <= eps [rho (24.3 S + 5.2) + 14 S + 9] / c + eps <= 84 eps rho S / c <= 168 eps rho Q / c = 2^-21.6 rho Q / c u,
+ * stated as kappa; the store rounds once more: 1 u, stated as k = 2 for the terms of second order.  m_c = n_c / D:
+ * |dn| / |n| + dD / |D| + eps <= 58 eps S / c <= 116 eps Q / c relative to |m|, inside kappa, and the store's u |m_c|.  beta: x^ =
+ * z^ d^ is off by |x| (dz / |z| + 3 eps) <= sqrt 3 P 93 eps rho S / c; it enters p = v_b - x and q = v_c - x alike, so p x q moves
+ * by dx x (v_b - v_c) and n . (p x q) / (n . n) by at most sqrt 3 L |dx| / |n| <= 279 eps rho Q S / c.  Apart from that p and q are
+ * off by eps L, p x q like n by 14 eps L^2, |p x q| <= 3 L^2; n . (p x q): 42 eps L^4 + 14 eps |n| L^2 + 15.6 eps |n| L^2; n . n and
+ * its reciprocal and the product: (28 S + 5) eps relative, |beta| <= 3 S.  Together
+ *   dbeta <= eps S [126 S + 44.6 + 279 rho Q / c] <= 1598 eps rho Q^2 / c = 2^-18.4 rho Q^2 / c u,
+ * stated as kappa_b, and the store's u |beta_a|, k = 2.  A void by n^ = 0 needs |n| <= |dn|, S >= 2^53 / 14; by
+ * D^ = 0, c <= eps (14 S + 9): either way Q / c >= 2^53 / 82 and kappa >= 2^25.
+ * AGAINST THE RENDER.  Where d_face_image is this handle's render of the same vertices and intrinsics, item (b) of its contract
+ * bounds the rendered depth against z(t^, s) at the clamped lambda, which is the z above when the pixel lies in the face (min
+ * lambda >= 0) and at most 9 tau_t R_t z away from it inside the coverage band.  So at every covered pixel
+ *   |z_row - z_rendered| <= (k + kappa) u |z| + (k_z + c_t) u z_rendered + [min lambda < 0] 9 tau_t R_t z:
+ * the sum of the two contracts.
+ * One thread per row, a gather of the face's 36 bytes of corners; plain stores, no atomics.  Asynchronous on `stream`, no host
+ * synchronisation, no workspace.  n_frames == 0 or N == 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL
+ * handle, negative n_frames or n_rows, fx or fy <= 0 or a non-finite intrinsic, d_offset without d_pixel, without d_pixel an
+ * n_rows other than n_frames H W, a uniform d_pixel whose n_rows n_frames does not divide, 2^31 - 4096 rows or more, and with
+ * rows to write: NULL d_face_image / d_index, NULL d_verts (n_faces > 0), a stride below 3 n_verts.                             */
+int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                     double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                     const int32_t* d_pixel /* may be NULL */, const int32_t* d_offset /* may be NULL */,
+                                     long long n_rows, int32_t* d_index, float* d_z /* may be NULL */,
+                                     float* d_bary /* may be NULL */, float* d_dir /* may be NULL */, void* stream);
 /* Statistics of the handle's latest render (from its read-back; no synchronisation): the (face, tile) pairs binned, and the
  * longest tile list.                                                                                                          */
 int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
