@@ -267,6 +267,8 @@ def load_library():
     lib.bodyfit_raster_depth_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
                                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_last_bins.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     _lib = lib
     return lib
@@ -946,6 +948,17 @@ class Raster:
                                                                float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
                                                                d_face_image_ptr, d_pixel_ptr, d_offset_ptr, int(n_rows),
                                                                d_index_ptr, d_z_ptr, d_bary_ptr, d_dir_ptr, stream))
+
+    def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_frame_stride: int, n_frames: int, invert: bool,
+                        d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_raster_distance_device: the exact squared Euclidean distance dist2 [F, H, W] int32 of every pixel to the
+        nearest seed of its frame and, unless None, nearest [F, H, W] int32, the linear index i W + j of a seed that attains it
+        (INT32_MAX and -1 in a frame without a seed).  seed_kind 0: u8 [F, H, W], a seed iff != 0; 1: int32 [F, H, W], a seed iff
+        >= 0 (a rendered face-id image); seed_frame_stride elements between frames; invert swaps seeds and non-seeds.
+        Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_distance_device(self.h, d_seed_ptr, int(seed_kind), int(seed_frame_stride),
+                                                             int(n_frames), int(bool(invert)), d_dist2_ptr, d_nearest_ptr,
+                                                             stream))
 
     def last_bins(self):
         """(face, tile) pairs binned by the latest render, and its longest tile list"""

@@ -16,6 +16,8 @@
 //   k_rs_depth_rows one thread per depth row (a pixel of a frame): the ray through the pixel against the plane of the face the
 //                face-id image holds there: z, the object-space barycentrics and the direction m with dz/dcorner_a = beta_a m
 //                (bodyfit_raster_depth_rows_device), f64 throughout, plain stores
+// bodyfit_raster_distance_device, the distance transform of masks and face-id images, has its host entry here, on the handle's
+// size and workspace; its kernels are k_edt.hip's (edt.h).
 //
 // Arithmetic.  The decision "does face t cover pixel s" and the depth order are taken in f64 from differences (corner - pixel),
 // never from coefficients of the whole image, so the cancellation is that of the face at the pixel; products are formed
@@ -33,6 +35,7 @@
 
 #include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
+#include "edt.h"
 #include "host_state.h"
 #include "solver_view.h"
 
@@ -291,9 +294,10 @@ struct bodyfit_raster {
   RsFace* d_recs = nullptr;      size_t recsCap = 0;      // records
   unsigned* d_tiles = nullptr;   size_t tilesCap = 0;     // tiles: count | cursor | offset
   int* d_entries = nullptr;      size_t entriesCap = 0;   // face ids
+  int32_t* d_edt = nullptr;      size_t edtCap = 0;       // distance transform: seed columns and envelope stacks (edt.h)
   unsigned lastTotals[2] = {0, 0};
   ~bodyfit_raster() {
-    for (void* q : {(void*)d_faces, (void*)d_totals, (void*)d_recs, (void*)d_tiles, (void*)d_entries})
+    for (void* q : {(void*)d_faces, (void*)d_totals, (void*)d_recs, (void*)d_tiles, (void*)d_entries, (void*)d_edt})
       if (q) (void)hipFree(q);
   }
 };
@@ -440,6 +444,30 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
   BODYFIT_LAUNCH(k_rs_depth_rows, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, d_verts, verts_frame_stride,
                  r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy, cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames,
                  n_rows, d_index, d_z, d_bary, d_dir);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_distance_device(bodyfit_raster* r, const void* d_seed, int seed_kind, long long seed_frame_stride,
+                                   int n_frames, int invert, int32_t* d_dist2, int32_t* d_nearest, void* stream) {
+  const char* fn = "bodyfit_raster_distance_device";
+  if (!r) return rs_invalid(fn, "handle is NULL");
+  if (n_frames < 0) return rs_invalid(fn, "negative n_frames");
+  if (seed_kind != 0 && seed_kind != 1) return rs_invalid(fn, "seed_kind must be 0 (u8) or 1 (int32)");
+  if (n_frames == 0) return BODYFIT_OK;
+  if (!d_seed || !d_dist2) return rs_invalid(fn, "d_seed or d_dist2 is NULL");
+  const long long ppf = (long long)r->W * r->H;
+  if (seed_frame_stride < ppf) return rs_invalid(fn, "seed_frame_stride below H W");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // groups of frames that share the workspace one after the other on the stream: its size follows from (F, H, W) alone
+  const int group = (int)std::max(1ll, std::min<long long>(n_frames, bodyfit::kEdtGroupPixels / ppf));
+  if (int rc = rs_grow(&r->d_edt, &r->edtCap, (size_t)group * ppf * bodyfit::kEdtWorkspaceInts)) return rc;
+  const size_t elem = seed_kind == 0 ? 1 : 4;
+  for (int f0 = 0; f0 < n_frames; f0 += group)
+    bodyfit::edt_launch(static_cast<const char*>(d_seed) + (size_t)f0 * seed_frame_stride * elem, seed_kind, seed_frame_stride,
+                        std::min(group, n_frames - f0), invert, r->W, r->H, r->d_edt, d_dist2 + (size_t)f0 * ppf,
+                        d_nearest ? d_nearest + (size_t)f0 * ppf : nullptr, st);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

@@ -748,7 +748,8 @@ int bodyfit_overlay_last_timing(bodyfit_overlay* ov, float ms[4]);
 /* ---- depth render and visibility (k_raster.hip): what one calibrated camera sees of the posed mesh ---------------------------
  * A bodyfit_raster holds one topology (faces: host int32 [n_faces][3], ids in [0, n_verts), else BODYFIT_ERR_INVALID; n_faces =
  * 0 is accepted) and one image size (1 .. 16384 each way) on one device, and the workspace of its calls, which grows on demand
- * (96 bytes per (frame, face), 12 per (frame, tile of 32 x 8 pixels), 4 per (face, tile) pair).                               */
+ * (96 bytes per (frame, face), 12 per (frame, tile of 32 x 8 pixels), 4 per (face, tile) pair; 8 per pixel of the frames of a
+ * distance transform).                                                                                                        */
 typedef struct bodyfit_raster bodyfit_raster;
 int bodyfit_raster_create(int device, int n_verts, int n_faces, const int32_t* faces, int width, int height,
                           bodyfit_raster** out);
@@ -888,6 +889,47 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
                                      const int32_t* d_pixel /* may be NULL */, const int32_t* d_offset /* may be NULL */,
                                      long long n_rows, int32_t* d_index, float* d_z /* may be NULL */,
                                      float* d_bary /* may be NULL */, float* d_dir /* may be NULL */, void* stream);
+/* DISTANCE TRANSFORM with the nearest seed (a feature transform) of n_frames masks of the handle's size (k_edt.hip): what a
+ * silhouette term needs of a person mask and of a rendered face-id image.  seed_kind 0: d_seed is u8 [n_frames][H][W] and a
+ * pixel is a SEED iff its byte is != 0 (a bool image qualifies); seed_kind 1: d_seed is int32 [n_frames][H][W] and a pixel is
+ * a seed iff its value is >= 0, so d_face of bodyfit_raster_render_device goes in as it is.  seed_frame_stride elements (bytes
+ * or int32) between frames, >= H W.  invert != 0 swaps seeds and non-seeds.  The topology is not used: a handle with n_faces = 0
+ * transforms masks without a mesh.  Outputs d_dist2 and, unless NULL, d_nearest: int32 [n_frames][H][W], dense, frame after frame.
+ * DEFINITION, exact, in integers, for pixel (row i, column j) of frame f:
+ *   dist2[f][i][j]   = min over the seeds (i', j') of frame f of (i - i')^2 + (j - j')^2,
+ *   nearest[f][i][j] = i' W + j' of a seed that ATTAINS that minimum.
+ * A seed pixel has dist2 0 and nearest itself.  A frame without a seed gets dist2 = INT32_MAX and nearest = -1 at every pixel.
+ * Range: sizes are at most 16384 each way, so dist2 <= 2 x 16383^2 < 2^29, and every intermediate below is under 2^30: int32.
+ * TIE RULE.  Among the seeds at the minimum the choice is a fixed function of the frame's mask: in a row the nearer seed column,
+ * the LEFT one when two are equally near; down a column the row that entered the lower envelope first keeps every pixel at
+ * which a later row only equals it.  So nearest is always the same one, but it is not "the lowest index": use it as A nearest
+ * seed.
+ * CONTRACT.  No tolerance: dist2 equals the definition at every pixel, and nearest is a seed of the same frame at exactly that
+ * squared distance.  Every output element is written, whatever the outputs held.  No atomics of any kind, plain stores: the
+ * results are bit-identical from run to run, and a frame's outputs depend on that frame only (identical whatever n_frames and
+ * the stride).
+ * Derivation.  Separable (Meijster, Roerdink, Hesselink 2000).  Row pass: c(i, j) = the seed column of row i nearest to j, from
+ * leading / trailing-zero counts of the row's seed bits: exact by construction.  With g_i = (j - c(i, j))^2, the minimum over the
+ * seeds of row i alone, dist2(x, j) = min_i F_i(x), F_i(x) = (x - i)^2 + g_i over the rows i that have a seed.  Column pass: the
+ * lower envelope of these parabolas as a stack of (i, t_i): row i is a minimiser for x in [t_i, t_next).  For rows i < u,
+ *   F_i(x) <= F_u(x)  <=>  2 x (u - i) <= u^2 - i^2 + g_u - g_i  <=>  x <= floor((u^2 - i^2 + g_u - g_i) / (2 (u - i)))
+ * for INTEGER x, because u - i > 0 and an integer is <= a rational iff it is <= its floor.  Numerator and denominator are exact
+ * int32 (below 2^30), and the quotient is the true floor (the truncated quotient, less one when the remainder is negative): no
+ * rounding occurs anywhere, so the boundary t_u = 1 + that floor is the first integer row at which u is STRICTLY better than i,
+ * not an approximation of the real intersection that could fall on the wrong side of an integer.  Row u pops the entries whose
+ * first row it already beats strictly (F_i(t_i) > F_u(t_i)), which is the same exact comparison, and is dropped when t_u >= H.
+ * Linear in the pixels: each row of a column is pushed and popped at most once.
+ * Shape: one wave per (frame, row), the seeds as 64-bit ballots in LDS; one lane per (frame, column), neighbouring lanes on
+ * neighbouring columns, the envelope stack in the workspace (8 bytes per pixel of a group of frames; the row pass's columns pass
+ * through d_dist2 itself; a call of more than 2^29 pixels is worked group after group on the stream, so the workspace never
+ * exceeds 4 GiB plus the slack of its growth).
+ * Asynchronous on `stream`, NO host synchronisation (the workspace size follows from n_frames, H, W on the host); a call that has
+ * to grow the workspace may synchronise, as the render does.  Calls on one handle share the workspace: order them.  n_frames ==
+ * 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames, seed_kind not 0 or 1, and
+ * with frames to write: NULL d_seed / d_dist2, a stride below H W.                                                             */
+int bodyfit_raster_distance_device(bodyfit_raster* r, const void* d_seed, int seed_kind, long long seed_frame_stride,
+                                   int n_frames, int invert, int32_t* d_dist2, int32_t* d_nearest /* may be NULL */,
+                                   void* stream);
 /* Statistics of the handle's latest render (from its read-back; no synchronisation): the (face, tile) pairs binned, and the
  * longest tile list.                                                                                                          */
 int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
