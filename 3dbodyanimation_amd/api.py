@@ -239,6 +239,9 @@ def load_library():
                                                        C.c_void_p]
     lib.bodyfit_surface_rows_vjp_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_surface_winding_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                                   C.c_longlong, C.c_void_p, C.c_void_p]
+    lib.bodyfit_surface_vertex_normals_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]
     lib.bodyfit_surface_gram_device.argtypes = [C.c_void_p, C.POINTER(PointSet), C.c_int, C.c_longlong, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong,
                                                 C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -748,7 +751,8 @@ class ClosestPoints:
 
 class Surface:
     """Closest point on the triangles of a posed mesh for every query point, and the gradient of the squared distances at the
-    fixed correspondence (bodyfit_surface_*, bodyfit_closest_surface_*, csrc/k_closest_surface.hip).  The handle holds one
+    fixed correspondence (bodyfit_surface_*, bodyfit_closest_surface_*, csrc/k_closest_surface.hip); the winding number of the
+    mesh about a point and its vertex normals (csrc/k_winding.hip).  The handle holds one
     topology (faces: int32 [n_faces, 3] with ids in [0, n_verts)) and the workspace of both calls; calls on one handle must be
     ordered (one stream, or events)."""
 
@@ -807,6 +811,22 @@ class Surface:
         _check(load_library().bodyfit_surface_rows_vjp_device(self.h, C.byref(rows), int(n_frames), int(n_rows_total), d_index_ptr,
                                                               d_bary_ptr, d_coef_ptr, d_dir_ptr, d_gverts_ptr,
                                                               int(gverts_frame_stride), stream))
+
+    def winding_device(self, query: PointSet, d_skip_vertex_ptr: int | None, d_verts_ptr: int, verts_frame_stride: int,
+                       n_frames: int, n_query_total: int, d_winding_ptr: int, stream: int | None = None):
+        """bodyfit_surface_winding_device: the winding number w [N] f32 of every query row about its frame's posed mesh (0
+        outside a closed, outward oriented mesh, 1 inside), asynchronous on `stream`.  d_skip_vertex_ptr: None, or int32 [N]
+        packed like w: row i leaves out the faces that have that vertex id among their corners (-1: none)."""
+        _check(load_library().bodyfit_surface_winding_device(self.h, C.byref(query), d_skip_vertex_ptr, d_verts_ptr,
+                                                             int(verts_frame_stride), int(n_frames), int(n_query_total),
+                                                             d_winding_ptr, stream))
+
+    def vertex_normals_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, d_normals_ptr: int,
+                              stream: int | None = None):
+        """bodyfit_surface_vertex_normals_device: the area-weighted unit vertex normals [F, n_verts, 3] f32 (dense) of the posed
+        mesh, 0 for a vertex without a face or with a zero sum; deterministic, asynchronous on `stream`."""
+        _check(load_library().bodyfit_surface_vertex_normals_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                                    d_normals_ptr, stream))
 
     def gram_device(self, query: PointSet, n_frames: int, n_query_total: int, d_index_ptr: int, d_bary_ptr: int,
                     d_weight_ptr: int | None, d_direction_ptr: int | None, d_jac_ptr: int, n_tangents: int, row_floats: int,

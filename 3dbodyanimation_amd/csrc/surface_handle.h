@@ -1,5 +1,6 @@
 // surface_handle.h — the bodyfit_surface handle, shared by the translation units that work on it: k_closest_surface.hip (create,
-// destroy, the searches and their VJP) and api_gram.hip (the Gauss-Newton normal equations at a fixed correspondence).
+// destroy, the searches and their VJP), api_gram.hip (the Gauss-Newton normal equations at a fixed correspondence) and
+// k_winding.hip (winding numbers and vertex normals).
 #pragma once
 #include "closest_group_inl.h"
 

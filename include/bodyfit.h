@@ -526,6 +526,67 @@ int bodyfit_closest_surface_vjp_device(bodyfit_surface* s, const bodyfit_pointse
 int bodyfit_surface_rows_vjp_device(bodyfit_surface* s, const bodyfit_pointset* rows, int n_frames, long long n_rows_total,
                                     const int32_t* d_index, const float* d_bary, const float* d_coef, const float* d_dir,
                                     float* d_gverts, long long gverts_frame_stride, void* stream);
+/* The WINDING NUMBER of the frame's posed mesh about every query point (k_winding.hip): is the point inside the body?  For a query
+ * p and a triangle t with corners v0, v1, v2 in the orientation of `faces`, a = v0 - p, b = v1 - p, c = v2 - p (van Oosterom and
+ * Strackee):    num = a . (b x c),    den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|,    Omega_t(p) = 2 atan2(num, den),
+ *   d_winding[i] = w(p_i) = (1 / 4 pi) sum over the frame's faces of Omega_t(p_i),      packed in frame order like d_dist2.
+ * atan2(0, 0) = 0: a face that has p as a corner contributes 0, and so does a face without an area.  For a closed, outward oriented
+ * mesh w is the number of times the surface encloses p (0 outside, 1 inside, 2 inside two overlapping parts); for an open mesh it
+ * is the generalised winding number and varies smoothly; reversing every face reverses the sign.
+ * d_skip_vertex (int32 [N], packed like d_winding, or NULL): row i leaves out the faces that have the id d_skip_vertex[i] >= 0
+ * among their three corner ids (a comparison of ids, not of positions); -1 skips none.  The VERTEX query is the uniform set
+ * {d_verts, n_verts, verts_frame_stride} with the ids 0 .. n_verts - 1 in every frame: then w_i = k_i + (the interior solid angle
+ * of the cone of faces about vertex i) / 4 pi, k_i the number of OTHER sheets of the surface that enclose the vertex and the cone's
+ * share strictly between 0 and 1, so vertex i lies inside another part of the body iff w_i > 1.
+ * A frame with a non-finite corner in any face gives NaN for every query row of that frame (whatever the rows skip); a non-finite
+ * query row gives NaN; other frames and rows are untouched.  n_faces = 0 gives 0.
+ * CONTRACT.  With u = 2^-24, l_t = |a||b||c| and z_t = den + i num, all exact from the f32 inputs, w* the exact value, and every
+ * distance from a query to a corner between 2^-40 and 2^40 or exactly 0 (no intermediate overflows or underflows),
+ *   |d_winding[i] - w*_i| <= B_i = (u / 2 pi) sum over the counted faces of (k l_t / |z_t| + k_s),        k = 64, k_s = 16.
+ * |z_t| = 0 with l_t > 0 happens exactly when p lies on an edge of t or in its plane across an edge at the angle where Omega
+ * jumps: there the bound is infinite and only a finite result is promised.  A face with l_t = 0 (p is a corner) has num = den = 0
+ * exactly, in f32 as in exact arithmetic, and counts k_s alone.  OUTSIDE that range of distances the result is UNDEFINED, and may be
+ * a finite number: finite corners far enough away overflow the products of three lengths, the arctangent then yields a NaN, and
+ * the integer sum takes that NaN's bits for a number.  Only non-finite INPUTS are promised to give NaN.
+ * Derivation (k_winding.hip; first order in u, the stated constants leave a tenth for the rest).  theta_t = atan2(num, den) is
+ * half the solid angle and w = sum theta_t / 2 pi, so an error e_t of theta_t moves w by e_t / 2 pi.  An error (dn, dd) of
+ * (num, den) turns theta by at most (|dn| + |dd|) / |z|.
+ *  num: a, b, c are one subtraction each (u per component).  A component of b x c is fma(x, y, -(z w)): the four inputs 2 u, the
+ *   product's rounding 1, the fused result's 1, each of at most |b||c|: 4 u |b||c| per component, 6.93 for the vector.  a . n is a
+ *   three-term fma chain: a's own u, n's 6.93, three roundings of partial sums <= |a||n|: |dn| <= 10.93 u l.
+ *  den: |a| = sqrt of a three-term chain of squares: the inputs 2 u, three roundings, halved by the root, the root's own rounding:
+ *   3.5 u; the product of three lengths 3 x 3.5 + 2 = 12.5 u l.  A dot a . b: inputs 2 u, roundings 3 u, of |a||b|; times a length
+ *   8.5 u l, three of them 25.5 u l.  The three fused additions round partial sums of at most 2 l, 3 l and 4 l: 9 u l.
+ *   |dd| <= 47 u l.                                                           Together 57.93 u l / |z|, stated as k = 64.
+ *  the arctangent, absolute, in u: mx, mn the larger and smaller of |num|, |den|; above tan(pi / 8) the argument is (mn - mx) / (mn +
+ *   mx): three roundings on |t| <= 0.4143, atan' <= 1: 1.25.  The polynomial t + t z P(z) (four coefficients) is within 0.14 of atan
+ *   there (tests/test_winding.py checks that figure of the coefficients), its evaluation costs 0.2 on the cubic part and 0.4 for
+ *   the last fused step.  + pi / 4: the constant 0.4, the sum 0.8.  pi / 2 - r: 0.73 and 1.57.  pi - r: 1.47 and 3.14.  Together 10.1.
+ *  the sum: theta is rounded to a multiple of 2^-32 (0.002) and added as an integer, EXACTLY; sum 2^-32 / 2 pi in f64 and one rounding
+ *   to f32, u |w| <= u n / 2 for n counted faces, that is pi in the units of k_s.        10.1 + 0.002 + 3.15 = 13.3, stated as k_s = 16.
+ * tests/winding_ref.py computes w* and B_i in f64 and restates the kernel's arithmetic in f32.  On a unit sphere of 2,560 faces
+ * next to a second one, B_i stays below 8e-4 at every vertex while w_i keeps 0.41 away from the threshold 1.
+ * Deterministic, and more: the sum is exact, so a row's bits do not depend on the split of the face range, on the wave a face fell
+ * to, on n_frames or on the frame's place in the batch: a frame's result is a function of that frame's data and counts only.  No
+ * atomics.  Query sets of either kind.  Workspace: with few query rows the face range is split and 8 bytes per (split, row) are
+ * kept; nothing per (frame, face).  Checks, asynchrony, ordering and the no-op rules are those of bodyfit_closest_surface_device
+ * (n_frames == 0 or no query rows: a successful no-op; BODYFIT_ERR_INVALID: NULL handle / set / d_winding, negative counts, a
+ * stride below 3 n_verts).  NOT differentiable: w is piecewise constant off the surface.                                      */
+int bodyfit_surface_winding_device(bodyfit_surface* s, const bodyfit_pointset* query, const int32_t* d_skip_vertex,
+                                   const float* d_verts, long long verts_frame_stride, int n_frames, long long n_query_total,
+                                   float* d_winding, void* stream);
+/* Area-weighted VERTEX NORMALS of the posed mesh (k_winding.hip):  n_i = normalise(sum over the faces t that hold vertex i of
+ * (v1 - v0) x (v2 - v0)), every face once and oriented as in `faces`; d_normals [F][n_verts][3] f32, dense.  A vertex without a
+ * face, with a zero sum or with a non-finite corner in one of its faces gets 0.  One thread per (frame, vertex) adds the faces in
+ * ascending order through the handle's vertex -> corner table in f64 (the differences of f32 corners are exact, the products are
+ * not fused, so a face that repeats a corner adds an exact zero), normalises in f64 and rounds ONCE:
+ *   |d_normals - n*| <= u + 2^-50 c_i per component,   c_i = sum |N_t| / |sum N_t| (how much the faces about the vertex cancel),
+ * u = 2^-24: one rounding of a number <= 1, and the f64 roundings of at most eight operations per face, amplified by c_i.
+ * Deterministic (no atomics; torch's index_add_ is not), frame-independent.  NOT differentiable: the oriented search uses the
+ * normals as a gate, which is piecewise constant.  Asynchronous on `stream`.  n_frames == 0 or n_verts == 0: a successful no-op.
+ * BODYFIT_ERR_INVALID: NULL handle / d_verts / d_normals, a negative n_frames, a stride below 3 n_verts.                      */
+int bodyfit_surface_vertex_normals_device(bodyfit_surface* s, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                          float* d_normals, void* stream);
 /* The Gauss-Newton NORMAL EQUATIONS of a scan term at a fixed correspondence, per frame, without ever holding a per-row Jacobian
  * (k_surface_gram.hip).  Row i of frame f (packed like d_dist2) carries d_index[i] = t_i, d_bary[i] = b_i, optionally a weight
  * w_i (d_weight [N] f32; NULL: 1) and a unit direction d_i (d_direction [N][3] f32; NULL: point-to-point).  d_jac is the dense
