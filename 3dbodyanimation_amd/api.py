@@ -215,6 +215,16 @@ def load_library():
     lib.bodyfit_forward_jvp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_longlong, C.c_void_p]
     lib.bodyfit_forward_jvp.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _dp, _fp]
+    lib.bodyfit_forward_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                   C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_forward_offsets_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                       C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_forward_offsets_jvp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_forward_offsets.argtypes = [C.c_void_p, _dp, _dp, _fp, C.c_longlong, _dp, _fp]
+    lib.bodyfit_forward_offsets_vjp.argtypes = [C.c_void_p, _dp, _dp, _fp, C.c_longlong, _fp, _dp, _dp, _dp, _fp]
+    lib.bodyfit_surface_laplacian_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p]
     lib.bodyfit_residuals_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.bodyfit_residual_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_void_p]
@@ -502,26 +512,51 @@ class Problem:
         _check(load_library().bodyfit_problem_views(self.h, C.byref(v)))
         return v
 
-    def forward(self, frame_params, beta=None, want_cloud=True):
+    def _offsets(self, offsets):
+        """Host offsets [V, 3] (shared by the frames) or [F, V, 3] as (contiguous f32 array, frame stride in floats)."""
+        o = np.ascontiguousarray(offsets, dtype=np.float32)
+        V = self.model.n_verts
+        if o.shape == (V, 3):
+            return o, 0
+        if o.shape == (self.n_frames, V, 3):
+            return o, 3 * V
+        raise ValueError(f"offsets must be [V, 3] or [F, V, 3], got {o.shape}")
+
+    def forward(self, frame_params, beta=None, want_cloud=True, offsets=None):
+        """Joints [F, nJ, 3] f64 and cloud [F, V, 3] f32 (bodyfit_forward).  offsets: per-vertex displacements [V, 3] or
+        [F, V, 3] f32 added to the blended rest vertices before skinning (bodyfit_forward_offsets; the joints do not move)."""
         self.generation += 1
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
         assert x.size >= self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         joints = np.empty((self.n_frames, self.model.n_joints, 3))
         cloud = np.empty((self.n_frames, self.model.n_verts, 3), np.float32) if want_cloud else None
-        _check(load_library().bodyfit_forward(self.h, _d(x), _d(b), _d(joints),
-                                              cloud.ctypes.data_as(_fp) if cloud is not None else None))
+        cp = cloud.ctypes.data_as(_fp) if cloud is not None else None
+        if offsets is None:
+            _check(load_library().bodyfit_forward(self.h, _d(x), _d(b), _d(joints), cp))
+        else:
+            o, stride = self._offsets(offsets)
+            _check(load_library().bodyfit_forward_offsets(self.h, _d(x), _d(b), o.ctypes.data_as(_fp), stride, _d(joints), cp))
         return joints, cloud
 
     def forward_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_joints_ptr: int | None, d_cloud_ptr: int | None,
-                       cloud_row_floats: int | None = None, stream: int | None = None):
-        """bodyfit_forward_device: the two-launch forward into device memory, asynchronous on `stream`."""
+                       cloud_row_floats: int | None = None, stream: int | None = None, d_offsets_ptr: int | None = None,
+                       offsets_frame_stride: int = 0):
+        """bodyfit_forward_device: the two-launch forward into device memory, asynchronous on `stream`.  d_offsets_ptr: f32
+        per-vertex offsets, [V, 3] (offsets_frame_stride 0) or rows of offsets_frame_stride floats per frame
+        (bodyfit_forward_offsets_device)."""
         self.generation += 1
         rf = 3 * self.model.n_verts if cloud_row_floats is None else int(cloud_row_floats)
-        _check(load_library().bodyfit_forward_device(self.h, d_params_ptr, d_beta_ptr, d_joints_ptr, d_cloud_ptr, rf, stream))
+        if d_offsets_ptr is None:
+            _check(load_library().bodyfit_forward_device(self.h, d_params_ptr, d_beta_ptr, d_joints_ptr, d_cloud_ptr, rf, stream))
+        else:
+            _check(load_library().bodyfit_forward_offsets_device(self.h, d_params_ptr, d_beta_ptr, d_offsets_ptr,
+                                                                 int(offsets_frame_stride), d_joints_ptr, d_cloud_ptr, rf, stream))
 
-    def forward_vjp(self, frame_params, beta=None, grad_cloud=None, grad_joints=None):
+    def forward_vjp(self, frame_params, beta=None, grad_cloud=None, grad_joints=None, offsets=None):
         """dL/dframe_params [F(+1), 7 + 3 (nJ - 1)] (76 for 24 joints) and dL/dbeta ([nS] shared, [F, nS] per frame; None
-        without the shape block) of the forward, given dL/dcloud [F, V, 3] and / or dL/djoints [F, nJ, 3] (bodyfit_forward_vjp)."""
+        without the shape block) of the forward, given dL/dcloud [F, V, 3] and / or dL/djoints [F, nJ, 3] (bodyfit_forward_vjp).
+        With offsets ([V, 3] or [F, V, 3]) the forward is the displaced one and a third result is dL/doffsets, f32 in the shape
+        of offsets (zeros without grad_cloud: the joints do not depend on the offsets; bodyfit_forward_offsets_vjp)."""
         x = _c64(frame_params); b = _c64(beta) if beta is not None else None
         assert x.size == self.n_param_rows * self.n_frame_params, "frame_params must be [F(+1), 7 + 3 (n_joints - 1)]"
         G = None if grad_cloud is None else np.ascontiguousarray(grad_cloud, dtype=np.float32)
@@ -535,17 +570,32 @@ class Problem:
         gb = None
         if has_beta:
             gb = np.empty((self.n_frames, self.model.n_shape)) if self.beta_per_frame else np.empty(self.model.n_shape)
-        _check(load_library().bodyfit_forward_vjp(self.h, _d(x), _d(b), G.ctypes.data_as(_fp) if G is not None else None,
-                                                  _d(H), _d(gx), _d(gb)))
-        return gx, gb
+        Gp = G.ctypes.data_as(_fp) if G is not None else None
+        if offsets is None:
+            _check(load_library().bodyfit_forward_vjp(self.h, _d(x), _d(b), Gp, _d(H), _d(gx), _d(gb)))
+            return gx, gb
+        o, stride = self._offsets(offsets)
+        go = np.zeros_like(o)
+        _check(load_library().bodyfit_forward_offsets_vjp(self.h, _d(x), _d(b), o.ctypes.data_as(_fp), stride, Gp, _d(H), _d(gx),
+                                                          _d(gb), go.ctypes.data_as(_fp) if G is not None else None))
+        return gx, gb, go
 
     def forward_vjp_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_grad_cloud_ptr: int | None,
                            d_grad_joints_ptr: int | None, d_grad_params_ptr: int, d_grad_beta_ptr: int | None,
-                           grad_cloud_row_floats: int | None = None, stream: int | None = None):
-        """bodyfit_forward_vjp_device: asynchronous on `stream`, device pointers throughout."""
+                           grad_cloud_row_floats: int | None = None, stream: int | None = None,
+                           d_offsets_ptr: int | None = None, offsets_frame_stride: int = 0, d_grad_offsets_ptr: int | None = None):
+        """bodyfit_forward_vjp_device: asynchronous on `stream`, device pointers throughout.  d_offsets_ptr /
+        offsets_frame_stride as forward_device; d_grad_offsets_ptr: f32 dL/doffsets in the layout of the offsets, or None
+        (bodyfit_forward_offsets_vjp_device)."""
         rf = 3 * self.model.n_verts if grad_cloud_row_floats is None else int(grad_cloud_row_floats)
-        _check(load_library().bodyfit_forward_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_cloud_ptr, rf,
-                                                         d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr, stream))
+        if d_offsets_ptr is None and d_grad_offsets_ptr is None:
+            _check(load_library().bodyfit_forward_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_grad_cloud_ptr, rf,
+                                                             d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr, stream))
+        else:
+            _check(load_library().bodyfit_forward_offsets_vjp_device(self.h, d_params_ptr, d_beta_ptr, d_offsets_ptr,
+                                                                     int(offsets_frame_stride), d_grad_cloud_ptr, rf,
+                                                                     d_grad_joints_ptr, d_grad_params_ptr, d_grad_beta_ptr,
+                                                                     d_grad_offsets_ptr, stream))
 
     def forward_jvp(self, frame_params, beta, tan_x, tan_beta=None, want_cloud=True):
         """Forward-mode tangents of the forward (bodyfit_forward_jvp): tan_x [F, K, 7 + 3 (nJ - 1)] (or None = 0) and tan_beta
@@ -573,11 +623,19 @@ class Problem:
 
     def forward_jvp_device(self, d_params_ptr: int, d_beta_ptr: int | None, n_tangents: int, d_tan_params_ptr: int | None,
                            d_tan_beta_ptr: int | None, d_tan_joints_ptr: int | None, d_tan_cloud_ptr: int | None,
-                           row_floats: int | None = None, stream: int | None = None):
-        """bodyfit_forward_jvp_device: asynchronous on `stream`, device pointers throughout."""
+                           row_floats: int | None = None, stream: int | None = None, d_offsets_ptr: int | None = None,
+                           offsets_frame_stride: int = 0):
+        """bodyfit_forward_jvp_device: asynchronous on `stream`, device pointers throughout.  d_offsets_ptr /
+        offsets_frame_stride as forward_device: the tangents are taken at the displaced point, the offsets themselves are
+        constants (bodyfit_forward_offsets_jvp_device)."""
         rf = 3 * self.model.n_verts if row_floats is None else int(row_floats)
-        _check(load_library().bodyfit_forward_jvp_device(self.h, d_params_ptr, d_beta_ptr, int(n_tangents), d_tan_params_ptr,
-                                                         d_tan_beta_ptr, d_tan_joints_ptr, d_tan_cloud_ptr, rf, stream))
+        if d_offsets_ptr is None:
+            _check(load_library().bodyfit_forward_jvp_device(self.h, d_params_ptr, d_beta_ptr, int(n_tangents), d_tan_params_ptr,
+                                                             d_tan_beta_ptr, d_tan_joints_ptr, d_tan_cloud_ptr, rf, stream))
+        else:
+            _check(load_library().bodyfit_forward_offsets_jvp_device(self.h, d_params_ptr, d_beta_ptr, d_offsets_ptr,
+                                                                     int(offsets_frame_stride), int(n_tangents), d_tan_params_ptr,
+                                                                     d_tan_beta_ptr, d_tan_joints_ptr, d_tan_cloud_ptr, rf, stream))
 
     def residuals_device(self, d_params_ptr: int, d_beta_ptr: int | None, d_residuals_ptr: int, d_comp_ptr: int | None = None,
                          keep_jacobian=False, stream: int | None = None):
@@ -827,6 +885,14 @@ class Surface:
         mesh, 0 for a vertex without a face or with a zero sum; deterministic, asynchronous on `stream`."""
         _check(load_library().bodyfit_surface_vertex_normals_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
                                                                     d_normals_ptr, stream))
+
+    def laplacian_device(self, d_field_ptr: int, field_stride: int, n_fields: int, d_out_ptr: int, transpose: bool = False,
+                         stream: int | None = None):
+        """bodyfit_surface_laplacian_device: the uniform mesh Laplacian l_i = x_i - mean over i's faces of the other two corners
+        (0 for a vertex without a face) of n_fields per-vertex fields [n_verts, 3] f32, field_stride floats apart, into the dense
+        [n_fields, n_verts, 3] f32 at d_out_ptr; transpose: the exact transpose.  Deterministic, asynchronous on `stream`."""
+        _check(load_library().bodyfit_surface_laplacian_device(self.h, d_field_ptr, int(field_stride), int(n_fields),
+                                                               int(bool(transpose)), d_out_ptr, stream))
 
     def gram_device(self, query: PointSet, n_frames: int, n_query_total: int, d_index_ptr: int, d_bary_ptr: int,
                     d_weight_ptr: int | None, d_direction_ptr: int | None, d_jac_ptr: int, n_tangents: int, row_floats: int,

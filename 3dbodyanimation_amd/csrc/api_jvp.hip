@@ -40,7 +40,17 @@ int jvp_problem_ready(bodyfit_problem* p) {
 int bodyfit_forward_jvp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, int n_tangents,
                                const double* d_tan_params, const double* d_tan_beta, double* d_tan_joints, float* d_tan_cloud,
                                long long row_floats, void* stream) {
+  return bodyfit_forward_offsets_jvp_device(p, d_frame_params, d_beta, nullptr, 0, n_tangents, d_tan_params, d_tan_beta,
+                                            d_tan_joints, d_tan_cloud, row_floats, stream);
+}
+
+int bodyfit_forward_offsets_jvp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                       const float* d_offsets, long long offsets_frame_stride, int n_tangents,
+                                       const double* d_tan_params, const double* d_tan_beta, double* d_tan_joints,
+                                       float* d_tan_cloud, long long row_floats, void* stream) {
   if (!p || !d_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  if (d_offsets)
+    if (int rc = check_offsets(p, offsets_frame_stride)) return rc;
   if (n_tangents < 1) return fail(BODYFIT_ERR_INVALID, "n_tangents < 1");
   if (!d_tan_joints && !d_tan_cloud) return fail(BODYFIT_ERR_INVALID, "both outputs are NULL");
   const bodyfit_model* m = p->m;
@@ -65,6 +75,7 @@ int bodyfit_forward_jvp_device(bodyfit_problem* p, const double* d_frame_params,
     const PriorArgs none{};
     launch_frame_resjac(m->d, p->d, d_frame_params, d_b, p->jvp_r, nullptr, p->jvp_joints, p->jvp_mc, 0, none, st);
     launch_jvp_blend(m->d, p->d, p->jvp_mc, p->jvp_bbuf, st);
+    if (d_offsets) launch_offsets_displace(m->d, p->d, d_offsets, offsets_frame_stride, p->jvp_bbuf, st);
     for (int t = 0; t < n_tiles; ++t) {   // one tangent tile of scratch per frame: chain and mesh alternate on the stream
       launch_jvp_chain(m->d, p->d, d_frame_params, d_b, K, t * 32, 1, d_tan_params, d_tb, per_frame, d_tan_joints, p->jvp_tdot,
                        p->jvp_featD, st);

@@ -609,10 +609,18 @@ int bodyfit_forward(bodyfit_problem* p, const double* frame_params, const double
 
 int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, double* d_joints,
                            float* d_cloud, long long cloud_row_floats, void* stream) {
+  return bodyfit_forward_offsets_device(p, d_frame_params, d_beta, nullptr, 0, d_joints, d_cloud, cloud_row_floats, stream);
+}
+
+int bodyfit_forward_offsets_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, const float* d_offsets,
+                                   long long offsets_frame_stride, double* d_joints, float* d_cloud, long long cloud_row_floats,
+                                   void* stream) {
   if (!p || !d_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
   const bodyfit_model* m = p->m;
   if (d_cloud && !p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "problem was created without want_mesh");
   if (d_cloud && cloud_row_floats < 3LL * m->V) return fail(BODYFIT_ERR_INVALID, "cloud_row_floats < 3 V");
+  if (d_offsets)
+    if (int rc = check_offsets(p, offsets_frame_stride)) return rc;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   p->async_stream = st;
@@ -629,9 +637,45 @@ int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, con
     const size_t row = (size_t)m->V * 3 * sizeof(float), pitch = (size_t)m->d.nVTiles * kVTile * 3 * sizeof(float);
     HIP_TRY(hipMemcpy2DAsync(d_cloud, (size_t)cloud_row_floats * sizeof(float), p->d_cloud, pitch, row, (size_t)p->d.F,
                              hipMemcpyDeviceToDevice, st));
+    if (d_offsets) launch_offsets_apply(m->d, p->d, p->mc, d_offsets, offsets_frame_stride, d_cloud, cloud_row_floats, st);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(BODYFIT_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return BODYFIT_OK;
+}
+
+int bodyfit_forward_offsets(bodyfit_problem* p, const double* frame_params, const double* beta, const float* offsets,
+                            long long offsets_frame_stride, double* joints, float* cloud) {
+  if (!offsets) return bodyfit_forward(p, frame_params, beta, joints, cloud);
+  if (!p || !frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  const bodyfit_model* m = p->m;
+  const auto [npose, has_beta, npar, nbeta_all] = dims(p);
+  if (cloud && !p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "problem was created without want_mesh");
+  if (int rc = check_offsets(p, offsets_frame_stride)) return rc;
+  HIP_TRY(hipSetDevice(m->device));
+  std::lock_guard<std::mutex> lock(p->mu);
+  p->cache_valid = false;
+  if (int ro = order_after_async(p, nullptr)) return ro;
+  const int F = p->d.F;
+  const size_t nbeta = (has_beta && beta) ? nbeta_all : 0;
+  const size_t nof = offsets_frame_stride ? (size_t)(F - 1) * (size_t)offsets_frame_stride + 3 * (size_t)m->V : 3 * (size_t)m->V;
+  const size_t njt = joints ? (size_t)F * m->nJ * 3 : 0, ncl = cloud ? (size_t)F * m->V * 3 : 0;
+  Allocs tmp;
+  double *d_x = nullptr, *d_b = nullptr, *d_j = nullptr;
+  float *d_o = nullptr, *d_c = nullptr;
+  HIP_TRY(tmp.alloc(&d_x, npar));
+  HIP_TRY(tmp.alloc(&d_o, nof));
+  if (nbeta) HIP_TRY(tmp.alloc(&d_b, nbeta));
+  if (njt) HIP_TRY(tmp.alloc(&d_j, njt));
+  if (ncl) HIP_TRY(tmp.alloc(&d_c, ncl));
+  HIP_TRY(hipMemcpy(d_x, frame_params, npar * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_o, offsets, nof * sizeof(float), hipMemcpyHostToDevice));
+  if (nbeta) HIP_TRY(hipMemcpy(d_b, beta, nbeta * sizeof(double), hipMemcpyHostToDevice));
+  if (int rc = bodyfit_forward_offsets_device(p, d_x, d_b, d_o, offsets_frame_stride, d_j, d_c, 3LL * m->V, nullptr)) return rc;
+  p->async_pending = false;   // (NULL stream, waited for below)
+  if (njt) HIP_TRY(hipMemcpy(joints, d_j, njt * sizeof(double), hipMemcpyDeviceToHost));
+  if (ncl) HIP_TRY(hipMemcpy(cloud, d_c, ncl * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipDeviceSynchronize());
   return BODYFIT_OK;
 }
 

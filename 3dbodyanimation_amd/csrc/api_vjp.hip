@@ -86,7 +86,19 @@ int vjp_problem_ready(bodyfit_problem* p, bool mesh) {
 int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
                                const float* d_grad_cloud, long long grad_cloud_row_floats, const double* d_grad_joints,
                                double* d_grad_frame_params, double* d_grad_beta, void* stream) {
+  return bodyfit_forward_offsets_vjp_device(p, d_frame_params, d_beta, nullptr, 0, d_grad_cloud, grad_cloud_row_floats,
+                                            d_grad_joints, d_grad_frame_params, d_grad_beta, nullptr, stream);
+}
+
+int bodyfit_forward_offsets_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                       const float* d_offsets, long long offsets_frame_stride, const float* d_grad_cloud,
+                                       long long grad_cloud_row_floats, const double* d_grad_joints, double* d_grad_frame_params,
+                                       double* d_grad_beta, float* d_grad_offsets, void* stream) {
   if (!p || !d_frame_params || !d_grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  if (d_grad_offsets && !d_offsets) return fail(BODYFIT_ERR_INVALID, "grad_offsets without offsets");
+  if (d_grad_offsets && !d_grad_cloud) return fail(BODYFIT_ERR_INVALID, "grad_offsets needs grad_cloud");
+  if (d_offsets)
+    if (int rc = check_offsets(p, offsets_frame_stride)) return rc;
   const bodyfit_model* m = p->m;
   const int npose = dims(p).npose, F = p->d.F, nS = m->nS;
   const bool has_beta = dims(p).has_beta;
@@ -106,6 +118,8 @@ int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params,
     const PriorArgs none{};
     launch_frame_resjac(m->d, p->d, d_frame_params, d_b, p->vjp_r, nullptr, p->vjp_joints, p->vjp_mc, 0, none, st);
     launch_vjp_mesh(m->d, p->d, p->vjp_mc, d_grad_cloud, grad_cloud_row_floats, p->vjp_gb, p->vjp_bbuf, st);
+    if (d_offsets) launch_offsets_displace(m->d, p->d, d_offsets, offsets_frame_stride, p->vjp_bbuf, st);
+    if (d_grad_offsets) launch_offsets_grad(m->d, p->d, p->vjp_gb, d_grad_offsets, offsets_frame_stride, st);
     launch_vjp_blend_t(m->d, p->d, p->vjp_gb, m->d_dirsT, p->vjp_part, st);
     launch_vjp_skin_t(m->d, p->d, m->d_csr_off, m->d_csr_v, m->d_csr_w, d_grad_cloud, grad_cloud_row_floats, p->vjp_bbuf,
                       p->vjp_dT, st);
@@ -124,7 +138,18 @@ int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params,
 
 int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* grad_cloud,
                         const double* grad_joints, double* grad_frame_params, double* grad_beta) {
+  return bodyfit_forward_offsets_vjp(p, frame_params, beta, nullptr, 0, grad_cloud, grad_joints, grad_frame_params, grad_beta,
+                                     nullptr);
+}
+
+int bodyfit_forward_offsets_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* offsets,
+                                long long offsets_frame_stride, const float* grad_cloud, const double* grad_joints,
+                                double* grad_frame_params, double* grad_beta, float* grad_offsets) {
   if (!p || !frame_params || !grad_frame_params) return fail(BODYFIT_ERR_INVALID, "null argument");
+  if (grad_offsets && !offsets) return fail(BODYFIT_ERR_INVALID, "grad_offsets without offsets");
+  if (grad_offsets && !grad_cloud) return fail(BODYFIT_ERR_INVALID, "grad_offsets needs grad_cloud");
+  if (offsets)
+    if (int rc = check_offsets(p, offsets_frame_stride)) return rc;
   const bodyfit_model* m = p->m;
   const int F = p->d.F, nS = m->nS;
   const auto [npose, has_beta, npar, nbeta_all] = dims(p);
@@ -139,7 +164,11 @@ int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const do
   // one temporary block: parameters, beta, upstream gradients, outputs
   Allocs tmp;
   double *d_x = nullptr, *d_b = nullptr, *d_gx = nullptr, *d_gb = nullptr, *d_H = nullptr;
-  float* d_G = nullptr;
+  float *d_G = nullptr, *d_o = nullptr, *d_go = nullptr;
+  const size_t nof = !offsets ? 0 : (offsets_frame_stride ? (size_t)(F - 1) * (size_t)offsets_frame_stride : 0) + 3 * (size_t)m->V;
+  if (nof) HIP_TRY(tmp.alloc(&d_o, nof));
+  if (nof && grad_offsets) HIP_TRY(tmp.alloc(&d_go, nof));
+  if (nof) HIP_TRY(hipMemcpy(d_o, offsets, nof * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(tmp.alloc(&d_x, npar));
   HIP_TRY(tmp.alloc(&d_gx, npar));
   if (nbeta) HIP_TRY(tmp.alloc(&d_b, nbeta));
@@ -151,8 +180,14 @@ int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const do
   if (ncl) HIP_TRY(hipMemcpy(d_G, grad_cloud, ncl * sizeof(float), hipMemcpyHostToDevice));
   if (njt) HIP_TRY(hipMemcpy(d_H, grad_joints, njt * sizeof(double), hipMemcpyHostToDevice));
   if (ngb) HIP_TRY(hipMemset(d_gb, 0, ngb * sizeof(double)));
-  if (int rc = bodyfit_forward_vjp_device(p, d_x, d_b, d_G, 3LL * m->V, d_H, d_gx, d_gb, nullptr)) return rc;
+  if (int rc = bodyfit_forward_offsets_vjp_device(p, d_x, d_b, d_o, offsets_frame_stride, d_G, 3LL * m->V, d_H, d_gx, d_gb, d_go,
+                                                  nullptr))
+    return rc;
   p->async_pending = false;   // (NULL stream, waited for below)
+  if (d_go) {   // the rows alone: what lies between rows longer than 3 V stays the caller's
+    const size_t row = 3 * (size_t)m->V * sizeof(float), pitch = offsets_frame_stride ? (size_t)offsets_frame_stride * sizeof(float) : row;
+    HIP_TRY(hipMemcpy2D(grad_offsets, pitch, d_go, pitch, row, offsets_frame_stride ? (size_t)F : 1, hipMemcpyDeviceToHost));
+  }
   HIP_TRY(hipMemcpy(grad_frame_params, d_gx, npar * sizeof(double), hipMemcpyDeviceToHost));
   if (ngb) HIP_TRY(hipMemcpy(grad_beta, d_gb, ngb * sizeof(double), hipMemcpyDeviceToHost));
   HIP_TRY(hipDeviceSynchronize());

@@ -380,6 +380,18 @@ void launch_jvp_chain(const DevModel& M, const DevProblem& P, const double* d_pa
 void launch_jvp_mesh(const DevModel& M, const DevProblem& P, const MeshCoef& mc, const uint16_t* d_featD, const float* d_tdot,
                      const float* d_bbuf, float* d_dbuf, int K, int k0, float* d_out, long long row_floats, hipStream_t s);
 
+// per-vertex offsets d (SMPL+D) of the forward and its two derivative pipelines (k_offsets.hip; bodyfit_forward_offsets*_device).
+// d_off [V][3] (off_stride 0: shared by the frames) or rows of off_stride >= 3 V floats per frame.
+// cloud rows += (sum_j W_vj T_j[:, :3]) d_v, on the transforms the forward left in mc.skinT
+void launch_offsets_apply(const DevModel& M, const DevProblem& P, const MeshCoef& mc, const float* d_off, long long off_stride,
+                          float* d_cloud, long long row_floats, hipStream_t s);
+// bbuf [F][Vp][3] += d: behind the VJP's stage a and the JVP's primal blend
+void launch_offsets_displace(const DevModel& M, const DevProblem& P, const float* d_off, long long off_stride, float* d_bbuf,
+                             hipStream_t s);
+// dL/dd from the VJP's gb ([Fp][3][Vp]): per frame a transposed copy, shared the frames' ascending f64 sum rounded once
+void launch_offsets_grad(const DevModel& M, const DevProblem& P, const float* d_gb, float* d_grad_off, long long off_stride,
+                         hipStream_t s);
+
 // vector-Jacobian product of the whole residual vector (k_residual_vjp.hip; bodyfit_residual_vjp_device)
 struct ResVjpArgs {
   int F, n_param_rows, ncols, npose, nS;

@@ -298,6 +298,17 @@ inline ProblemDims dims(const bodyfit_problem* p) {
                      has_beta ? (size_t)(p->desc.beta_per_frame ? p->d.F * p->m->nS : p->m->nS) : 0};
 }
 
+// The preconditions of per-vertex offsets, shared by bodyfit_forward_offsets*: a want_mesh problem, SMPL's 24 joints (the
+// skinning transforms' stride in k_offsets.hip), and a frame stride of 0 (shared) or at least one dense row.  (A call without
+// its cloud argument ignores valid offsets: the joints do not depend on them.)
+inline int check_offsets(const bodyfit_problem* p, long long offsets_frame_stride) {
+  if (p->m->nJ != kMaxJoints) return fail(BODYFIT_ERR_INVALID, "offsets need a model with 24 joints");
+  if (!p->desc.want_mesh) return fail(BODYFIT_ERR_INVALID, "offsets need a problem created with want_mesh");
+  if (offsets_frame_stride != 0 && offsets_frame_stride < 3LL * p->m->V)
+    return fail(BODYFIT_ERR_INVALID, "offsets_frame_stride is neither 0 (shared) nor >= 3 V");
+  return BODYFIT_OK;
+}
+
 // What one sweep() evaluates, where, and where its results go.
 struct SweepRequest {
   const double* params;           // device

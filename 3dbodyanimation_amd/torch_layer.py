@@ -85,6 +85,16 @@ pairs of query and triangle, the half solid angles summed exactly as integers); 
 vertices with their own faces left out, where w > 1 means "inside another part of the body" without a threshold.
 SelfPenetrationTerm matches those vertices, through the oriented search with minus their normal (vertex_normals,
 bodyfit_surface_vertex_normals_device), to the sheet they have passed through, and pulls them back out.
+
+    verts, joints = layer(x, beta, offsets=d)                            # SMPL+D: d [V, 3] or [F, V, 3] f32, differentiable
+    reg = OffsetRegulariser(faces, w_smooth=1e3, w_norm=1.0)             # w_smooth sum |L d|^2 + w_norm sum |d|^2
+    (term(verts) + reg(d)).backward()
+
+Every data term above measures a naked body against a clothed person.  offsets displaces the blended rest vertex before
+skinning (bodyfit_forward_offsets*_device, k_offsets.hip); the joints, and with them FitObjective's keypoint landmarks, stay those
+of the undisplaced shape.  layer.jvp / layer.jacobian / forward_ad and every normal_equations take offsets= as a constant, so a
+Gauss-Newton step on pose and shape alternates with gradient steps on the offsets.  mesh_laplacian is
+bodyfit_surface_laplacian_device, a deterministic gather whose backward is the transposed gather.
 """
 from __future__ import annotations
 
@@ -149,6 +159,69 @@ class _SMPLForward(torch.autograd.Function):
                                         g_joints.data_ptr() if g_joints is not None else None,
                                         gx.data_ptr(), gb.data_ptr(), 3 * ctx.n_verts, _stream())
         return (gx if want_x else None), (gb if want_b else None), None, None, None
+
+
+class _SMPLForwardOffsets(torch.autograd.Function):
+    """_SMPLForward with per-vertex offsets [V, 3] or [F, V, 3] f32 as a third differentiable input (bodyfit_forward_offsets*)."""
+
+    @staticmethod
+    def forward(ctx, x, beta, offsets, prob, n_verts, n_joints):
+        F = x.shape[0]
+        verts = torch.empty((F, n_verts, 3), dtype=torch.float32, device=x.device)
+        joints = torch.empty((F, n_joints, 3), dtype=torch.float64, device=x.device)
+        stride = 3 * n_verts if offsets.ndim == 3 else 0
+        prob.forward_device(x.data_ptr(), beta.data_ptr(), joints.data_ptr(), verts.data_ptr(), 3 * n_verts, _stream(),
+                            d_offsets_ptr=offsets.data_ptr(), offsets_frame_stride=stride)
+        ctx.prob = prob
+        ctx.n_verts = n_verts
+        ctx.stride = stride
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, beta, offsets)
+        ctx.save_for_forward(x, beta, offsets)
+        return verts, joints
+
+    @staticmethod
+    def jvp(ctx, x_t, beta_t, offsets_t, *_):
+        if offsets_t is not None:
+            raise NotImplementedError("the offsets carry no tangent: forward-mode AD treats them as constants")
+        x, beta, offsets = ctx.saved_tensors
+        F = x.shape[0]
+        n_joints = (x.shape[1] - 7) // 3 + 1
+        verts_t = torch.empty((F, ctx.n_verts, 3), dtype=torch.float32, device=x.device)
+        joints_t = torch.empty((F, n_joints, 3), dtype=torch.float64, device=x.device)
+        if x_t is not None:
+            x_t = x_t.to(torch.float64).contiguous()
+        if beta_t is not None:
+            beta_t = beta_t.to(torch.float64).contiguous()
+        ctx.prob.forward_jvp_device(x.data_ptr(), beta.data_ptr(), 1, x_t.data_ptr() if x_t is not None else None,
+                                    beta_t.data_ptr() if beta_t is not None else None, joints_t.data_ptr(),
+                                    verts_t.data_ptr(), 3 * ctx.n_verts, _stream(), d_offsets_ptr=offsets.data_ptr(),
+                                    offsets_frame_stride=ctx.stride)
+        return verts_t, joints_t
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_verts, g_joints):
+        x, beta, offsets = ctx.saved_tensors
+        want_x, want_b, want_o = ctx.needs_input_grad[:3]
+        if g_verts is not None:
+            g_verts = g_verts.to(torch.float32).contiguous()
+        if g_joints is not None:
+            g_joints = g_joints.to(torch.float64).contiguous()
+        gx = torch.empty_like(x)
+        gb = torch.empty_like(beta)
+        # (without a gradient on the vertices the offsets get zeros: the joints do not depend on them)
+        go = (torch.empty_like(offsets) if g_verts is not None else torch.zeros_like(offsets)) if want_o else None
+        if g_verts is None and g_joints is None:
+            gx.zero_(); gb.zero_()
+        else:
+            ctx.prob.forward_vjp_device(x.data_ptr(), beta.data_ptr(),
+                                        g_verts.data_ptr() if g_verts is not None else None,
+                                        g_joints.data_ptr() if g_joints is not None else None,
+                                        gx.data_ptr(), gb.data_ptr(), 3 * ctx.n_verts, _stream(),
+                                        d_offsets_ptr=offsets.data_ptr(), offsets_frame_stride=ctx.stride,
+                                        d_grad_offsets_ptr=go.data_ptr() if (go is not None and g_verts is not None) else None)
+        return (gx if want_x else None), (gb if want_b else None), go, None, None, None
 
 
 class SMPLLayer(torch.nn.Module):
@@ -225,16 +298,42 @@ class SMPLLayer(torch.nn.Module):
             raise ValueError(f"x and beta must be on cuda:{self.model.device}")
         return F
 
-    def forward(self, x: torch.Tensor, beta: torch.Tensor):
-        F = self._check(x, beta)
-        return _SMPLForward.apply(x.contiguous(), beta.contiguous(), self.problem(F), self.model.n_verts, self.model.n_joints)
+    def _check_offsets(self, offsets, x, F):
+        """the checked offsets, contiguous: f32 on x's GPU, [V, 3] (shared by the frames) or [F, V, 3]"""
+        V = self.model.n_verts
+        if not isinstance(offsets, torch.Tensor):
+            raise TypeError("offsets must be a torch tensor")
+        if offsets.dtype != torch.float32:
+            raise TypeError("offsets must be float32")
+        if not offsets.is_cuda or offsets.device != x.device:
+            raise ValueError(f"offsets must be on cuda:{self.model.device}")
+        if tuple(offsets.shape) not in ((V, 3), (F, V, 3)):
+            raise ValueError(f"offsets must be [{V}, 3] or [{F}, {V}, 3], got {list(offsets.shape)}")
+        if self.model.n_joints != 24:
+            raise ValueError("offsets need a model with 24 joints")
+        return offsets.contiguous()
 
-    def jvp(self, x: torch.Tensor, beta: torch.Tensor, tan_x: torch.Tensor | None, tan_beta: torch.Tensor | None = None):
+    def forward(self, x: torch.Tensor, beta: torch.Tensor, offsets: torch.Tensor | None = None):
+        """(verts [F, V, 3] f32, joints [F, nJ, 3] f64).  offsets: None, or per-vertex displacements f32 on the same GPU, [V, 3]
+        shared by the frames or [F, V, 3], added to the blended rest vertex before skinning (SMPL+D); differentiable like x and
+        beta, with an f32 gradient of its own shape.  The joints are those of the undisplaced shape."""
+        F = self._check(x, beta)
+        if offsets is None:
+            return _SMPLForward.apply(x.contiguous(), beta.contiguous(), self.problem(F), self.model.n_verts, self.model.n_joints)
+        offsets = self._check_offsets(offsets, x, F)
+        return _SMPLForwardOffsets.apply(x.contiguous(), beta.contiguous(), offsets, self.problem(F), self.model.n_verts,
+                                         self.model.n_joints)
+
+    def jvp(self, x: torch.Tensor, beta: torch.Tensor, tan_x: torch.Tensor | None, tan_beta: torch.Tensor | None = None,
+            offsets: torch.Tensor | None = None):
         """Forward-mode tangents of forward(x, beta) along K tangents at once (bodyfit_forward_jvp_device, HIP kernels in
         k_forward_jvp.hip; nothing is recorded for autograd): tan_x [F, K, 76] f64 (None: zero) and tan_beta [K, nS], or
         [F, K, nS] with beta_per_frame (None: zero), give (tan_verts [F, K, V, 3] f32, tan_joints [F, K, nJ, 3] f64).  The result
-        for a (frame, tangent) pair does not depend on F, K or the tangent's position, bit for bit."""
+        for a (frame, tangent) pair does not depend on F, K or the tangent's position, bit for bit.  offsets (as forward's): the
+        tangents are those of forward(x, beta, offsets) with the offsets held constant."""
         F = self._check(x, beta)
+        if offsets is not None:
+            offsets = self._check_offsets(offsets, x, F).detach()
         nS = self.model.n_shape
         if tan_x is None and tan_beta is None:
             raise ValueError("give tan_x or tan_beta")
@@ -267,13 +366,15 @@ class SMPLLayer(torch.nn.Module):
         tan_joints = torch.empty((F, K, nJ, 3), dtype=torch.float64, device=x.device)
         self.problem(F).forward_jvp_device(x.data_ptr(), beta.data_ptr(), K, tan_x.data_ptr() if tan_x is not None else None,
                                            tan_beta.data_ptr() if tan_beta is not None else None, tan_joints.data_ptr(),
-                                           tan_verts.data_ptr(), 3 * V, _stream())
+                                           tan_verts.data_ptr(), 3 * V, _stream(),
+                                           d_offsets_ptr=offsets.data_ptr() if offsets is not None else None,
+                                           offsets_frame_stride=3 * V if (offsets is not None and offsets.ndim == 3) else 0)
         return tan_verts, tan_joints
 
-    def jacobian(self, x: torch.Tensor, beta: torch.Tensor):
+    def jacobian(self, x: torch.Tensor, beta: torch.Tensor, offsets: torch.Tensor | None = None):
         """The dense Jacobian of forward(x, beta): jvp with the P = 76 + nS unit tangents.  (Jv [F, P, V, 3] f32,
         Jj [F, P, nJ, 3] f64); slice p < 76 is the derivative w.r.t. frame parameter p of that frame, slice 76 + i the
-        derivative w.r.t. beta_i (of that frame's beta with beta_per_frame, of the shared beta otherwise)."""
+        derivative w.r.t. beta_i (of that frame's beta with beta_per_frame, of the shared beta otherwise).  offsets: as jvp's."""
         F = self._check(x, beta)
         nP, nS = api.N_FRAME_PARAMS, self.model.n_shape
         P = nP + nS
@@ -282,7 +383,7 @@ class SMPLLayer(torch.nn.Module):
         tan_beta = None
         if nS > 0:
             tan_beta = eye[:, nP:].expand(F, P, nS).contiguous() if self.beta_per_frame else eye[:, nP:].contiguous()
-        return self.jvp(x, beta, tan_x, tan_beta)
+        return self.jvp(x, beta, tan_x, tan_beta, offsets=offsets)
 
 
 def huber_rho(delta: float, s: torch.Tensor) -> torch.Tensor:
@@ -523,12 +624,12 @@ class PointCloudTerm(torch.nn.Module):
             cost = cost + _rho_sum(*closest_points(verts, self.points, ref_offset=self.offset), self.trunc)
         return cost
 
-    def normal_equations(self, layer: "SMPLLayer", x: torch.Tensor, beta: torch.Tensor, frame_chunk: int = 32):
+    def normal_equations(self, layer: "SMPLLayer", x: torch.Tensor, beta: torch.Tensor, frame_chunk: int = 32, offsets=None):
         """(cost, g [F, P], H [F, P, P]), f64: the Gauss-Newton normal equations of 1/2 term(verts) at the current closest
         vertices, as SurfaceTerm.normal_equations gives them for the surface term (conventions there).  A scan point's
         counterpart is a vertex, so the kernel sees a list of one-corner pseudo-faces (v, v, v) with the weights (1, 0, 0); the
         bidirectional half (every vertex against its closest scan point) is the same call with a diagonal W."""
-        return _normal_equations(self, layer, x, beta, frame_chunk, lambda verts: self._jobs(verts))
+        return _normal_equations(self, layer, x, beta, frame_chunk, lambda verts: self._jobs(verts), offsets)
 
     def _jobs(self, verts):
         F, V = verts.shape[0], verts.shape[1]
@@ -762,7 +863,7 @@ class SurfaceTerm(torch.nn.Module):
 
 
     def normal_equations(self, layer: "SMPLLayer", x: torch.Tensor, beta: torch.Tensor, mode: str = "point",
-                         frame_chunk: int = 32):
+                         frame_chunk: int = 32, offsets=None):
         """The Gauss-Newton normal equations of the term at (x, beta): (cost, g [F, P], H [F, P, P]), f64, P = 76 + nS in the
         column order of SMPLLayer.jacobian, per frame.  With a shared beta the caller sums the beta rows and columns (76 ..) of g
         and H over the frames, the convention of bodyfit_frame_normals.
@@ -779,10 +880,11 @@ class SurfaceTerm(torch.nn.Module):
         reused) and surface_gram on it: nothing here grows with F P V (torch's temporaries of the rows grow with the number of
         scan points, the library's buffers with frame_chunk).  A layer with a per-frame R0 gives every chunk a problem of its
         own, one at a time (SMPLLayer.chunk_problem): a create and a destroy, with a device synchronisation, per chunk.  No
-        autograd; on torch.cuda.current_stream()."""
+        autograd; on torch.cuda.current_stream().  offsets (as SMPLLayer.forward's): the equations of pose and shape at the
+        displaced body, the offsets held constant (they have no columns)."""
         if mode not in ("point", "plane"):
             raise ValueError('mode must be "point" or "plane"')
-        return _normal_equations(self, layer, x, beta, frame_chunk, lambda verts: self._jobs(verts, mode))
+        return _normal_equations(self, layer, x, beta, frame_chunk, lambda verts: self._jobs(verts, mode), offsets)
 
     def _jobs(self, verts, mode):
         F, V = verts.shape[0], verts.shape[1]
@@ -943,6 +1045,71 @@ def vertex_normals(verts: torch.Tensor, faces) -> torch.Tensor:
         with torch.cuda.device(v.device):
             handle.vertex_normals_device(v.data_ptr(), vs.frame_stride, F, n.data_ptr(), _stream())
     return n
+
+
+class _MeshLaplacian(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, handle):
+        ctx.handle = handle
+        return _laplacian(field, handle, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return _laplacian(g.to(torch.float32).contiguous(), ctx.handle, True), None
+
+
+def _laplacian(field: torch.Tensor, handle, transpose: bool) -> torch.Tensor:
+    n = field.numel() // (3 * handle.n_verts) if handle.n_verts > 0 else 0
+    out = torch.empty_like(field)
+    if out.numel() > 0:
+        with torch.cuda.device(field.device):
+            handle.laplacian_device(field.data_ptr(), 3 * handle.n_verts, n, out.data_ptr(), transpose, _stream())
+    return out
+
+
+def mesh_laplacian(field: torch.Tensor, faces) -> torch.Tensor:
+    """The uniform Laplacian of a per-vertex field [V, 3] or [K, V, 3] f32 on the GPU over the topology `faces` (int32
+    [n_faces, 3] on the host, or an api.Surface): l_i = x_i - (1 / 2 n_i) sum over the n_i faces that hold i of their other two
+    corners, an interior vertex minus the mean of its ring; 0 for a vertex without a face (bodyfit_surface_laplacian_device:
+    a gather in f64 in a fixed order).  Differentiable: the backward is the transposed gather, as deterministic as the forward
+    (torch's index_add_ is not)."""
+    if not isinstance(field, torch.Tensor):
+        raise TypeError("field must be a torch tensor")
+    if field.dtype != torch.float32:
+        raise TypeError("field must be float32")
+    if not field.is_cuda:
+        raise ValueError("field must be on the GPU")
+    if field.ndim not in (2, 3) or field.shape[-1] != 3:
+        raise ValueError(f"field must be [V, 3] or [K, V, 3], got {tuple(field.shape)}")
+    handle = _surface_handle(field.device.index, field.shape[-2], faces)
+    return _MeshLaplacian.apply(field.contiguous(), handle)
+
+
+class OffsetRegulariser(torch.nn.Module):
+    """w_smooth sum |L d|^2 + w_norm sum |d|^2 (f64) of per-vertex offsets d [V, 3] or [F, V, 3] f32, L the uniform mesh Laplacian
+    of `faces` (mesh_laplacian): what keeps an offset field a garment and not noise.  The keypoint landmarks and the joints do
+    not see the offsets, so without this term the vertices no data term reaches are free."""
+
+    def __init__(self, faces, w_smooth: float = 1.0, w_norm: float = 0.0):
+        super().__init__()
+        if w_smooth < 0.0 or w_norm < 0.0:
+            raise ValueError("the weights must be non-negative")
+        self.faces = _host_faces(faces).copy()
+        self.w_smooth = float(w_smooth)
+        self.w_norm = float(w_norm)
+        self._handles: dict[tuple, object] = {}
+
+    def forward(self, offsets: torch.Tensor) -> torch.Tensor:
+        handle = self.faces
+        if isinstance(offsets, torch.Tensor) and offsets.is_cuda and offsets.ndim in (2, 3):
+            key = (offsets.device.index, offsets.shape[-2])
+            handle = self._handles.get(key)
+            if handle is None:
+                handle = self._handles[key] = _surface_handle(key[0], key[1], self.faces)
+        lap = mesh_laplacian(offsets, handle).double()
+        d = offsets.double()
+        return self.w_smooth * (lap * lap).sum() + self.w_norm * (d * d).sum()
 
 
 class _SignedRoot(torch.autograd.Function):
@@ -1331,14 +1498,14 @@ class DepthResidualTerm(torch.nn.Module):
             s = torch.clamp(s, max=self.trunc * self.trunc)
         return s.sum()
 
-    def normal_equations(self, layer: "SMPLLayer", x: torch.Tensor, beta: torch.Tensor, frame_chunk: int = 32):
+    def normal_equations(self, layer: "SMPLLayer", x: torch.Tensor, beta: torch.Tensor, frame_chunk: int = 32, offsets=None):
         """The Gauss-Newton normal equations of the term at (x, beta): (cost, g [F, P], H [F, P, P]), f64, in the conventions of
         SurfaceTerm.normal_equations.  cost = 1/2 sum_i w_i r_i^2 + 1/2 trunc^2 (the truncated rows) = 1/2 term(verts), w_i the gate
         and the truncation indicator [r_i^2 < trunc^2]; a depth row is a point-to-plane row with the weights bary_i on its face's
         corners, the unit direction m_i / |m_i| and the weight w_i |m_i|^2 (dr_i/dverts = bary_ia m_i), so H = sum_i w_i
         (dr_i/dtheta)^T (dr_i/dtheta) comes from surface_gram as it is, and g = J^T rhs with rhs = sum_i w_i r_i bary_ia m_i from
         the rows VJP: the reverse-mode gradient of the same cost through the layer."""
-        return _normal_equations(self, layer, x, beta, frame_chunk, self._jobs)
+        return _normal_equations(self, layer, x, beta, frame_chunk, self._jobs, offsets)
 
     def _jobs(self, verts):
         F, V = verts.shape[0], verts.shape[1]
@@ -1661,8 +1828,18 @@ def surface_gram(jac: torch.Tensor, points: torch.Tensor, index: torch.Tensor, b
     return H, g
 
 
-def _normal_equations(term, layer, x, beta, frame_chunk, jobs_of):
-    """the shared body of the terms' normal_equations: forward, the term's jobs, then the Jacobian and the Gram chunk by chunk"""
+def _chunk_offsets(offsets, f0: int, V: int) -> dict:
+    """a chunk problem's offset arguments for the frames from f0 on (nothing without offsets: today's call)"""
+    if offsets is None:
+        return {}
+    if offsets.ndim == 2:
+        return {"d_offsets_ptr": offsets.data_ptr(), "offsets_frame_stride": 0}
+    return {"d_offsets_ptr": offsets[f0:].data_ptr(), "offsets_frame_stride": 3 * V}
+
+
+def _normal_equations(term, layer, x, beta, frame_chunk, jobs_of, offsets=None):
+    """the shared body of the terms' normal_equations: forward, the term's jobs, then the Jacobian and the Gram chunk by chunk
+    (offsets: constant per-vertex displacements of the forward and of the Jacobian's point, sliced with the frames)"""
     if not isinstance(layer, SMPLLayer):
         raise TypeError("layer must be an SMPLLayer")
     if not isinstance(frame_chunk, int) or isinstance(frame_chunk, bool) or frame_chunk < 1:
@@ -1675,7 +1852,9 @@ def _normal_equations(term, layer, x, beta, frame_chunk, jobs_of):
     P = nP + nS
     with torch.no_grad():
         x, beta = x.detach().contiguous(), beta.detach().contiguous()
-        verts, _ = layer(x, beta)
+        if offsets is not None:
+            offsets = layer._check_offsets(offsets, x, F).detach()
+        verts, _ = layer(x, beta, offsets)
         cost, rhs, jobs = jobs_of(verts)
         dev = x.device
         chunk = min(frame_chunk, F)
@@ -1694,7 +1873,7 @@ def _normal_equations(term, layer, x, beta, frame_chunk, jobs_of):
             # (tan_x and a per-frame tan_beta are [chunk, P, .]: their first n frames are the unit tangents of n frames)
             layer.chunk_problem(f0, n).forward_jvp_device(x[f0:f1].data_ptr(), b.data_ptr(), P, tan_x.data_ptr(),
                                                           tan_beta.data_ptr() if tan_beta is not None else None, None,
-                                                          work.data_ptr(), 3 * V, _stream())
+                                                          work.data_ptr(), 3 * V, _stream(), **_chunk_offsets(offsets, f0, V))
             for k, job in enumerate(jobs):
                 pts, off, rows = job.chunk(f0, f1)
                 Hc, gc = surface_gram(work[:n], pts, job.index[rows], job.bary[rows], job.handle, query_offset=off,

@@ -306,6 +306,60 @@ int bodyfit_forward_jvp_device(bodyfit_problem* p, const double* d_frame_params,
 int bodyfit_forward_jvp(bodyfit_problem* p, const double* frame_params, const double* beta, int n_tangents,
                         const double* tan_params, const double* tan_beta, double* tan_joints, float* tan_cloud);
 
+/* ---- per-vertex offsets (SMPL+D) -------------------------------------------------------------------------------------------
+ * A displacement d_v per vertex, added to the blended rest vertex before skinning (k_offsets.hip):
+ *   cloud_v = sum_j W_vj T_j [b_v + d_v; 1] = cloud0_v + L_fv d_v,   L_fv = sum_j W_vj T_j[:, :3] = s Rr0 (blended rotations),
+ * cloud0 = bodyfit_forward_device's cloud.  T_j, b_v and the JOINTS are those of the undisplaced shape (the usual SMPL+D
+ * convention: the joints are regressed from template + shapedirs beta, so d_joints, the keypoint landmarks, the one-launch sweep
+ * and the solvers do not see d).  L_fv does not depend on beta.
+ *   d_offsets f32: [V][3] shared by the frames (offsets_frame_stride = 0), or frame f's [V][3] at d_offsets + f
+ *   offsets_frame_stride (>= 3 V).  NULL: every function below IS the function it extends, launch for launch (the functions
+ *   above call these with NULL).  Offsets need the mesh path: a want_mesh problem and a model with 24 joints; a call without its
+ *   cloud argument (d_cloud / d_grad_cloud / d_tan_cloud) ignores valid offsets, since nothing else depends on them.
+ * bodyfit_forward_offsets_device: the two-launch forward into the caller's rows, then k_offsets_apply on those rows: one
+ *   thread per (frame, vertex) blends the vertex's four transforms (the f32 ones the forward left behind, the frame's 24 x 12
+ *   floats staged once per workgroup) as the VJP's k_vjp_vertex_grad does and adds L_fv d_v in place.  A vertex with d_v == 0 is
+ *   not touched, so zero offsets give bodyfit_forward_device's cloud bit for bit.  Frame-independent (frame f's rows are
+ *   bit-identical whatever F).  Error against the exact delta = L_fv d_v, per component, both clouds from the device:
+ *     |cloud_d - cloud0 - delta| <= 2^-24 (16 |s| |d_v|_1 + |cloud_d|):
+ *   every entry of L is <= |s| in magnitude and carries the rounding of its f32 transform entries (1), of the weights (1), of
+ *   the four blend products and sums (4, fewer where the compiler fuses) and of the three products and two sums with d (3 at
+ *   most counted against |s| |d_v|_1): about 9 u |s| |d_v|_1, u = 2^-24; the final sum cloud0 + delta rounds once, u |cloud_d|.
+ * bodyfit_forward_offsets_vjp_device: bodyfit_forward_vjp_device of the displaced forward.  k_offsets_displace adds d to the
+ *   blended rest vertices between stage a and stage c, so dL/dT_j = sum_v W_vj G_v [b_v + d_v; 1]^T; stage b's input gb_v =
+ *   L_fv^T G_v does not depend on d and is untouched.  d_grad_offsets (f32, the layout and stride of d_offsets; NULL: not wanted)
+ *   receives dL/dd: per-frame offsets gb_fv itself, shared offsets sum_f gb_fv, the frames added in ascending order in f64 and
+ *   rounded once (no atomics: bit-identical from run to run, and equal to that sum of the per-frame result bit for bit).
+ *   Error against the exact sum_f L_fv^T G_fv per component: <= 2^-24 (16 sum_f |s_f| |G_fv|_1 + |dL/dd|), by the count above
+ *   with G in the place of d, plus the one final rounding.  Rows of d_grad_offsets longer than 3 V: the rest is not written.
+ *   d_grad_offsets without d_grad_cloud is BODYFIT_ERR_INVALID (chosen over writing zeros: a gradient on the joints alone does
+ *   not reach the offsets, and a caller who asks for it has most likely dropped an argument).
+ * bodyfit_forward_offsets_jvp_device: bodyfit_forward_jvp_device at the displaced point; the same displace kernel between the
+ *   primal blend and the skinning tangent, clouddot_v = sum_j W_vj (Tdot_j [b_v + d_v; 1] + T_j[:, :3] bdot_v).  The offsets are
+ *   constants: they carry no tangent.  Tolerances as bodyfit_forward_jvp_device.
+ * Otherwise each takes the arguments, ordering rules and errors of the function it extends, and in addition
+ * BODYFIT_ERR_INVALID: offsets without want_mesh, offsets with n_joints != 24, a stride in (0, 3 V), d_grad_offsets without
+ * d_offsets or without d_grad_cloud.                                                                                       */
+int bodyfit_forward_offsets_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta, const float* d_offsets,
+                                   long long offsets_frame_stride, double* d_joints, float* d_cloud, long long cloud_row_floats,
+                                   void* stream);
+int bodyfit_forward_offsets_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                       const float* d_offsets, long long offsets_frame_stride, const float* d_grad_cloud,
+                                       long long grad_cloud_row_floats, const double* d_grad_joints, double* d_grad_frame_params,
+                                       double* d_grad_beta, float* d_grad_offsets, void* stream);
+int bodyfit_forward_offsets_jvp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
+                                       const float* d_offsets, long long offsets_frame_stride, int n_tangents,
+                                       const double* d_tan_params, const double* d_tan_beta, double* d_tan_joints,
+                                       float* d_tan_cloud, long long row_floats, void* stream);
+/* Host-pointer forms, synchronous (cloud and gradient rows of 3 V floats; offsets and grad_offsets with the given stride: as in
+ * the device form only the first 3 V floats of a grad_offsets row are written).  With offsets the forward is the two-launch one
+ * of bodyfit_forward_offsets_device; with NULL offsets they are bodyfit_forward and bodyfit_forward_vjp.                     */
+int bodyfit_forward_offsets(bodyfit_problem* p, const double* frame_params, const double* beta, const float* offsets,
+                            long long offsets_frame_stride, double* joints, float* cloud);
+int bodyfit_forward_offsets_vjp(bodyfit_problem* p, const double* frame_params, const double* beta, const float* offsets,
+                                long long offsets_frame_stride, const float* grad_cloud, const double* grad_joints,
+                                double* grad_frame_params, double* grad_beta, float* grad_offsets);
+
 /* ---- the fitting objective as a differentiable function of (frame_params, beta) ----------------------------------------
  * Residual vector into caller memory: the sweep at (frame_params, beta) (without the mesh), then an asynchronous copy of the
  * problem's residuals [total_rows] (bodyfit_problem_layout row order) to d_residuals and, if d_gmm_comp [F] is not NULL, of the
@@ -587,6 +641,20 @@ int bodyfit_surface_winding_device(bodyfit_surface* s, const bodyfit_pointset* q
  * BODYFIT_ERR_INVALID: NULL handle / d_verts / d_normals, a negative n_frames, a stride below 3 n_verts.                      */
 int bodyfit_surface_vertex_normals_device(bodyfit_surface* s, const float* d_verts, long long verts_frame_stride, int n_frames,
                                           float* d_normals, void* stream);
+/* The uniform mesh LAPLACIAN of per-vertex fields (k_offsets.hip), the smoothness operator of an offset field's regulariser:
+ * field k is [n_verts][3] f32 at d_field + k field_stride (>= 3 n_verts), d_out [n_fields][n_verts][3] f32, dense, not d_field.
+ * With n_i the number of faces that hold vertex i (a face that repeats i counted once) and a, b the face's other two corner
+ * POSITIONS (taken from i's first position in it):
+ *   l_i = x_i - (1 / 2 n_i) sum_{t holds i} (x_a + x_b),   l_i = 0 when n_i = 0   (an interior vertex: x_i - mean of its ring).
+ * transpose = 1 applies the exact transpose:  (L^T r)_u = [n_u > 0] r_u - sum_{t holds u} sum_{other corners v} r_v / (2 n_v)
+ * (for a vertex without a face both its row and its column of L are zero, so both directions give it 0).
+ * One thread per (field, vertex) gathers over the vertex's entries of the handle's vertex -> corner table in ascending order, in
+ * f64, and rounds once: |d_out - exact| <= 2^-24 |exact| + 2^-48 sum |x| over the vertex and its ring.  No atomics (torch's
+ * index_add_ is not deterministic, and not needed), field-independent.  Asynchronous on `stream`.  n_fields == 0 or n_verts == 0:
+ * a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / d_field / d_out, d_out == d_field, a negative n_fields, a stride
+ * below 3 n_verts.                                                                                                          */
+int bodyfit_surface_laplacian_device(bodyfit_surface* s, const float* d_field, long long field_stride, int n_fields,
+                                     int transpose, float* d_out, void* stream);
 /* The Gauss-Newton NORMAL EQUATIONS of a scan term at a fixed correspondence, per frame, without ever holding a per-row Jacobian
  * (k_surface_gram.hip).  Row i of frame f (packed like d_dist2) carries d_index[i] = t_i, d_bary[i] = b_i, optionally a weight
  * w_i (d_weight [N] f32; NULL: 1) and a unit direction d_i (d_direction [N][3] f32; NULL: point-to-point).  d_jac is the dense
