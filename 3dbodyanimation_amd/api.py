@@ -282,6 +282,12 @@ def load_library():
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_shade_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                                C.c_void_p]
+    lib.bodyfit_raster_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_double,
+                                                 C.c_double, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_last_bins.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     _lib = lib
     return lib
@@ -982,7 +988,8 @@ class Overlay:
 
 
 class Raster:
-    """Depth and face-id render of the posed mesh on the device, and face / vertex visibility from a face-id image
+    """Depth and face-id render of the posed mesh on the device, face / vertex visibility from a face-id image, per-vertex
+    attributes shaded over a render and images sampled at projected points
     (bodyfit_raster_*, csrc/k_raster.hip; the definition and its contract: include/bodyfit.h).  The handle holds one topology
     (faces: int32 [n_faces, 3] with ids in [0, n_verts)), one image size and the workspace; calls on one handle must be
     ordered (one stream, or events)."""
@@ -1045,6 +1052,36 @@ class Raster:
         _check(load_library().bodyfit_raster_distance_device(self.h, d_seed_ptr, int(seed_kind), int(seed_frame_stride),
                                                              int(n_frames), int(bool(invert)), d_dist2_ptr, d_nearest_ptr,
                                                              stream))
+
+    def shade_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                     d_attr_ptr: int | None, attr_frame_stride: int, n_channels: int, n_frames: int, background,
+                     d_image_ptr: int, d_weight_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_raster_shade_device: per-vertex attributes (rows of n_channels f32, 1 .. 4; attr_frame_stride floats between
+        frames, 0: shared by the frames) interpolated perspective-correct over a face-id image [F, H, W] int32 with weights
+        bary [F, H, W, 3] f32: image [F, H, W, n_channels] f32 and, unless None, the object-space weights [F, H, W, 3] f32.
+        background: a float or up to four floats (a void pixel's value).  Asynchronous on `stream`, no host synchronisation."""
+        bg = np.zeros(4, np.float32)
+        b = np.atleast_1d(np.asarray(background, np.float32))
+        if b.ndim != 1 or b.shape[0] > 4:
+            raise ValueError("background is a float or up to four floats")
+        bg[:4 if b.shape[0] == 1 else b.shape[0]] = b          # (one float: every channel)
+        _check(load_library().bodyfit_raster_shade_device(self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride),
+                                                          d_attr_ptr, int(attr_frame_stride), int(n_channels), int(n_frames),
+                                                          bg.ctypes.data_as(C.POINTER(C.c_float)), d_image_ptr, d_weight_ptr,
+                                                          stream))
+
+    def sample_device(self, d_points_ptr: int, points_frame_stride: int, n_points: int, n_frames: int, intr, d_image_ptr: int,
+                      image_kind: int, n_channels: int, image_frame_stride: int, d_gate_ptr: int | None, d_value_ptr: int,
+                      d_valid_ptr: int, d_grad_ptr: int | None = None, z_near: float = 0.1, stream: int | None = None):
+        """bodyfit_raster_sample_device: the images [F, H, W, n_channels] (image_kind 0: u8, raw 0 .. 255; 1: f32;
+        image_frame_stride elements between frames) read bilinearly at the projections of points [F, n_points, 3] f32: value
+        [F, n_points, n_channels] f32, valid [F, n_points] u8 and, unless None, grad [F, n_points, n_channels, 2] f32 = (d/du,
+        d/dv); gate u8 [F, n_points] or None.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_sample_device(self.h, d_points_ptr, int(points_frame_stride), int(n_points),
+                                                           int(n_frames), float(intr[0]), float(intr[1]), float(intr[2]),
+                                                           float(intr[3]), float(z_near), d_image_ptr, int(image_kind),
+                                                           int(n_channels), int(image_frame_stride), d_gate_ptr, d_value_ptr,
+                                                           d_valid_ptr, d_grad_ptr, stream))
 
     def last_bins(self):
         """(face, tile) pairs binned by the latest render, and its longest tile list"""

@@ -1059,6 +1059,81 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
 int bodyfit_raster_distance_device(bodyfit_raster* r, const void* d_seed, int seed_kind, long long seed_frame_stride,
                                    int n_frames, int invert, int32_t* d_dist2, int32_t* d_nearest /* may be NULL */,
                                    void* stream);
+/* VERTEX ATTRIBUTES OVER A RENDER (k_rs_shade, k_raster.hip): per-vertex attributes (colours) interpolated over a face-id image,
+ * perspective-correct.  d_face int32 [n_frames][H][W] and d_bary f32 [n_frames][H][W][3]: a render of this handle's topology and
+ * size, or hand-made images.  d_verts f32 [n_frames][n_verts][3], verts_frame_stride floats between frames (>= 3 n_verts); only
+ * the z of the corners is read.  d_attr f32 rows of n_channels floats per vertex, n_channels in 1 .. 4; attr_frame_stride floats
+ * between frames: 0 when the frames share one set of attributes, else >= n_channels n_verts.  background: 4 floats on the HOST, read
+ * before the call returns (NULL: 0).  Outputs d_image f32 [n_frames][H][W][n_channels] and, unless NULL, d_weight f32
+ * [n_frames][H][W][3], dense.  Every element of every frame is written, whatever the buffers held.
+ * DEFINITION, exact from the f32 inputs.  At a pixel let t be its face id, ids = faces[t], Z_a the z of corner a, lambda_a its
+ * three weights in d_bary, q_a = lambda_a / Z_a and S = sum_a q_a.  The pixel is VOID iff t is outside [0, n_faces), or some
+ * lambda_a or Z_a is not finite, or some Z_a <= 0, or some lambda_a < 0, or S = 0.  A void pixel gets background[c] and weights 0.
+ * Otherwise w_a = q_a / S and image[c] = sum_a w_a attr[ids[a]][c].  The w_a are the perspective-correct OBJECT-space weights of
+ * the pixel's ray in the face: >= 0 and of sum 1 by construction; with the lambda of bodyfit_raster_render_device they are
+ * lambda_a z / Z_a, z the rendered depth, up to that render's contract.  Attributes are plain IEEE: a NaN attribute gives NaN in
+ * the pixels that use it.  d_weight is the (index, bary) of bodyfit_surface_rows_vjp_device for the gradient in the attributes.
+ * CONTRACT, with u = 2^-24, k_s = 2 and per pixel and channel T_c = sum_a w_a |attr[ids[a]][c]|:
+ *   |image^_c - image_c| <= k_s u T_c,        |w^_a - w_a| <= k_s u w_a
+ * (for results in f32's normal range; one below 2^-126 is rounded to the subnormal grid, 2^-150 at most away).
+ * Derivation (eps = 2^-53 = 2^-29 u; every operation f64, products and sums separately rounded, never fused).  The conversions
+ * of lambda, Z and attr to f64 are exact.  Every q_a is >= 0, so nothing below cancels.  A quotient q_a: 1 eps.  S, two sums of
+ * non-negative numbers: 3 eps.  w_a = q_a / S: 1 + 3 + 1 = 5 eps.  A product w_a attr_ac: 6 eps |w_a attr_ac|.  The channel's two
+ * sums: 8 eps T_c.  The store rounds once: u |image^_c| <= u (1 + 8 eps) T_c.  Together (1 + 2^-25) u T_c, stated as k_s = 2; a
+ * weight is 5 eps and the store's u: the same k_s.
+ * One thread per pixel, neighbouring lanes on neighbouring columns; each gathers the face's three ids, three z and 3 n_channels
+ * attributes (neighbouring pixels mostly share a face); plain stores, no atomics, no workspace: bit-identical from run to run, and
+ * a frame's image depends on that frame only (bit-identical whatever n_frames; with or without d_weight).  Asynchronous on
+ * `stream`, no host synchronisation.  n_frames == 0: a successful no-op; n_faces == 0: every pixel background.
+ * BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames, n_channels outside 1 .. 4, and with frames to write:
+ * NULL d_face / d_bary / d_image, NULL d_verts or d_attr (n_faces > 0), a vertex stride below 3 n_verts, a non-zero attribute
+ * stride below n_channels n_verts, 2^39 pixels or more.                                                                        */
+int bodyfit_raster_shade_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                long long verts_frame_stride, const float* d_attr, long long attr_frame_stride, int n_channels,
+                                int n_frames, const float* background /* host [4]; may be NULL */, float* d_image,
+                                float* d_weight /* may be NULL */, void* stream);
+/* IMAGE SAMPLES AT PROJECTED POINTS (k_rs_sample, k_raster.hip): a batch of images read bilinearly where the points of a cloud
+ * project, with the image gradient there.  The topology is not used: a handle with n_faces = 0 samples images (of its size), as
+ * it transforms masks.  d_points f32 [n_frames][n_points][3], points_frame_stride floats between frames (>= 3 n_points:
+ * bodyfit_device_views.cloud is used in place); intrinsics in f64 (fx, fy > 0), z_near > 0.  d_image: image_kind 0 = u8, 1 = f32,
+ * [n_frames][H][W][n_channels] interleaved, n_channels in 1 .. 4, image_frame_stride ELEMENTS between frames (>= H W n_channels);
+ * a u8 texel is its raw value 0 .. 255, not scaled.  d_gate u8 [n_frames][n_points] or NULL.  Outputs d_value f32
+ * [n_frames][n_points][n_channels], d_valid u8 [n_frames][n_points] and, unless NULL, d_grad f32 [n_frames][n_points]
+ * [n_channels][2] = (d/du, d/dv).  Every element is written; an invalid point gets 0 everywhere.
+ * DEFINITION.  (u, v) = (fx X / Z + cx, fy Y / Z + cy); pixel centres at integers, the render's convention.  A point is LIVE iff
+ * X, Y, Z are finite, Z >= z_near, its gate byte is non-zero (or d_gate is NULL), 0 <= u <= W - 1 and 0 <= v <= H - 1.  For a live
+ * point j0 = min(floor(u), max(W - 2, 0)), j1 = min(j0 + 1, W - 1), a = u - j0, and i0, i1, b alike in v, H;
+ *   value_c = (1 - a)(1 - b) I[i0][j0] + a (1 - b) I[i0][j1] + (1 - a) b I[i1][j0] + a b I[i1][j1],
+ *   d/du    = (1 - b)(I[i0][j1] - I[i0][j0]) + b (I[i1][j1] - I[i1][j0]),
+ *   d/dv    = (1 - a)(I[i1][j0] - I[i0][j0]) + a (I[i1][j1] - I[i0][j1]):
+ * the exact derivative of the bilinear patch of the cell (i0, j0) (at u = W - 1 the last cell's, from the left; W = 1: 0).
+ * CONTRACT, with u = 2^-24, P = max(W, H) + max(|cx|, |cy|), delta = 2^-50 P and M the largest |texel| among the texels of the
+ * exact cell and of the returned cell:
+ *   (a) a point that is live and at least delta inside the border is returned live; a point returned live lies within delta of
+ *       the closed rectangle [0, W - 1] x [0, H - 1]; the tests on Z, on the gate and on finiteness are exact;
+ *   (b) |value^ - B(u, v)| <= u |B| + 2^-46 P M, B the continuous bilinear surface through the texels;
+ *   (c) there is a cell K whose closed support is within delta of the exact (u, v) such that each returned derivative is within
+ *       u |g_K| + 2^-46 P M of the derivative g_K of K's patch at (u, v).
+ * Derivation (eps = 2^-53; every operation f64 and unfused).  u^: the quotient, the product and the sum round once each, 3 eps P
+ * = 2^-51.4 P, as in the render's derivation: inside delta.  The comparisons and floor act on u^, which gives (a), and the
+ * returned cell K holds (u^, v^) in its closed support, within delta of (u, v).  a = u^ - j0 is exact (Sterbenz, or j0 = 0 and a =
+ * u^).  B is continuous and piecewise bilinear, of slope at most 2 M per pixel in each coordinate, and equals K's patch at (u^,
+ * v^): moving from (u, v) to (u^, v^), at most delta each way, changes it by at most 4 M delta = 2^-48 P M.  The patch evaluated in
+ * f64: 1 - a, four products of two weights, four products with texels, three sums: below 8 eps M.  Together below 2^-47 P M,
+ * stated as 2^-46 P M; the store rounds once: u |B|.  A derivative of K's patch is linear in the other coordinate with slope at
+ * most 4 M: 4 M delta = 2^-48 P M for the move, differences of texels are exact for u8 and 1 eps for f32, two products and a sum:
+ * below 8 eps M; the store's u |g_K|.
+ * One thread per (frame, point); the 4 n_channels texels are gathered before anything is combined.  Plain stores, no atomics, no
+ * workspace: bit-identical from run to run, and a frame's outputs depend on that frame only.  Asynchronous on `stream`, no host
+ * synchronisation.  n_frames == 0 or n_points == 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle,
+ * negative n_frames or n_points, n_channels outside 1 .. 4, image_kind outside {0, 1}, z_near <= 0 or NaN, fx or fy <= 0 or a
+ * non-finite intrinsic, and with points to write: NULL d_points / d_image / d_value / d_valid, a point stride below 3 n_points,
+ * an image stride below H W n_channels, 2^39 points or more.                                                                 */
+int bodyfit_raster_sample_device(bodyfit_raster* r, const float* d_points, long long points_frame_stride, long long n_points,
+                                 int n_frames, double fx, double fy, double cx, double cy, float z_near, const void* d_image,
+                                 int image_kind, int n_channels, long long image_frame_stride,
+                                 const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
+                                 float* d_grad /* may be NULL */, void* stream);
 /* Statistics of the handle's latest render (from its read-back; no synchronisation): the (face, tile) pairs binned, and the
  * longest tile list.                                                                                                          */
 int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
