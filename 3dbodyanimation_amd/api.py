@@ -289,6 +289,14 @@ def load_library():
                                                  C.c_double, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_int, C.c_int,
                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_last_bins.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+    lib.bodyfit_raster_edges_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_edge_blend_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                     C.c_void_p]
+    lib.bodyfit_raster_edge_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                                    C.c_double, C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1082,6 +1090,39 @@ class Raster:
                                                            float(intr[3]), float(z_near), d_image_ptr, int(image_kind),
                                                            int(n_channels), int(image_frame_stride), d_gate_ptr, d_value_ptr,
                                                            d_valid_ptr, d_grad_ptr, stream))
+
+    def edges_device(self, d_verts_ptr: int | None, verts_frame_stride: int, n_frames: int, intr, d_face_ptr: int | None,
+                     d_depth_ptr: int | None, d_weight_ptr: int, z_near: float = 0.1, cull_backfaces: bool = False,
+                     stream: int | None = None):
+        """bodyfit_raster_edges_device: the silhouette-edge antialiasing weights [F, H, W, 2] f32 (per pixel its right and lower
+        pair: > 0 the neighbour receives, < 0 the pixel receives, 0 no blend) of a render (face [F, H, W] int32, depth [F, H, W]
+        f32) of the vertices [F, n_verts, 3] f32.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_edges_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                          float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
+                                                          float(z_near), int(bool(cull_backfaces)), d_face_ptr, d_depth_ptr,
+                                                          d_weight_ptr, stream))
+
+    def edge_blend_device(self, d_weight_ptr: int, d_image_ptr: int, n_channels: int, n_frames: int, transpose: bool,
+                          d_out_ptr: int, stream: int | None = None):
+        """bodyfit_raster_edge_blend_device: out [F, H, W, n_channels] f32 = the image blended by the weights of edges_device, or
+        with transpose the adjoint of that map applied to the image.  Asynchronous on `stream`."""
+        _check(load_library().bodyfit_raster_edge_blend_device(self.h, d_weight_ptr, d_image_ptr, int(n_channels), int(n_frames),
+                                                               int(bool(transpose)), d_out_ptr, stream))
+
+    def edge_rows_device(self, d_verts_ptr: int | None, verts_frame_stride: int, n_frames: int, intr, d_face_ptr: int | None,
+                         d_depth_ptr: int | None, d_image_ptr: int | None, d_grad_ptr: int | None, n_channels: int,
+                         d_pair_ptr: int, d_offset_ptr: int | None, n_pairs: int, d_index_ptr: int, d_bary_ptr: int,
+                         d_coef_ptr: int, d_dir_ptr: int, z_near: float = 0.1, cull_backfaces: bool = False,
+                         stream: int | None = None):
+        """bodyfit_raster_edge_rows_device: for the listed pairs (pair [N] int32 = 2 pixel + axis, offset [F + 1] int32 or None)
+        the two rows (index [2 N] int32, bary [2 N, 3], coef [2 N], dir [2 N, 3] f32) of the blend's gradient in the two corners
+        of the pair's silhouette edge, from the image and the upstream gradient [F, H, W, n_channels] f32; index -1: the pair does
+        not blend.  Asynchronous on `stream`."""
+        _check(load_library().bodyfit_raster_edge_rows_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                              float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
+                                                              float(z_near), int(bool(cull_backfaces)), d_face_ptr, d_depth_ptr,
+                                                              d_image_ptr, d_grad_ptr, int(n_channels), d_pair_ptr, d_offset_ptr,
+                                                              int(n_pairs), d_index_ptr, d_bary_ptr, d_coef_ptr, d_dir_ptr, stream))
 
     def last_bins(self):
         """(face, tile) pairs binned by the latest render, and its longest tile list"""

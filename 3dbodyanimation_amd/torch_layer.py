@@ -107,6 +107,16 @@ backward bodyfit_surface_rows_vjp_device over the pixels.  sample_images is body
 vertex and frame, u8 or f32 images, with the image gradient of the cell).  fuse_vertex_colours averages the samples of the frames
 that see a vertex, weighted by the cosine to the camera; PhotometricTerm holds such colours against the frames and is
 differentiable in the vertices and in the colours.
+
+    soft = antialias(image, verts, faces, intr)                          # silhouette edges blended: a gradient to image AND verts
+    w = edge_weights(verts, faces, intr, (H, W))                         # [F, H, W, 2]: the blend's weights, no gradient
+    term = CoverageTerm(mask, intr, faces)                               # sum (antialias(covered) - mask)^2, pixel^2
+
+Every render above is piecewise constant in the vertices.  antialias is bodyfit_raster_edges_device (k_raster.hip: per pair of
+neighbouring pixels owned by different faces, a bounded walk to the nearer face's silhouette edge and the fraction of the segment
+between the two centres it cuts off) followed by bodyfit_raster_edge_blend_device; its backward is that blend transposed for the
+image and, for the vertices, bodyfit_raster_edge_rows_device into bodyfit_surface_rows_vjp_device.  Only coverage carries a
+gradient: the interpolation inside a face does not.  CoverageTerm is the exact-outline counterpart of SilhouetteTerm.
 """
 from __future__ import annotations
 
@@ -1837,7 +1847,7 @@ def render_attributes(verts: torch.Tensor, faces, intr, size, attr: torch.Tensor
     include/bodyfit.h.
 
     Differentiable in attr ONLY, at the fixed render: NOT differentiable in verts (neither through the weights nor through
-    visibility or coverage).  The backward is bodyfit_surface_rows_vjp_device with the pixels as rows (index = the face image,
+    visibility or coverage; antialias(image, verts, ...) adds the gradient through coverage).  The backward is bodyfit_surface_rows_vjp_device with the pixels as rows (index = the face image,
     bary = the stored weights, coef = 1, direction = the upstream gradient, three channels per call: C = 4 takes two); shared
     attributes get the frames' gradients summed in f64.  No float atomics, no index_add_: bit-identical from run to run."""
     _check_verts(verts)
@@ -1848,6 +1858,189 @@ def render_attributes(verts: torch.Tensor, faces, intr, size, attr: torch.Tensor
     if bg.ndim != 1 or bg.shape[0] not in (1, C):
         raise ValueError(f"background must be a float or {C} floats")
     return _RenderAttributes.apply(attr, verts, faces, intr, size, bg, float(z_near), bool(cull_backfaces))
+
+
+# ---- silhouette-edge antialiasing: the render's coverage as a smooth function of the vertices -----------------------------------
+def _render_or(render, verts, faces, intr, size, z_near, cull_backfaces):
+    """(raster handle, depth [F, H, W] f32, face [F, H, W] int32) of verts: `render` (what render_depth returned, or (depth,
+    face)) checked and used as it is, or a fresh render"""
+    H, W = int(size[0]), int(size[1])
+    if render is None:
+        raster, depth, face, _ = _render(verts, faces, intr, (H, W), z_near, cull_backfaces, False)
+        return raster, depth, face
+    if len(render) < 2:
+        raise ValueError("render is (depth, face) or (depth, face, bary), as render_depth returns them")
+    depth, face = render[0], render[1]
+    F = verts.shape[0]
+    for t, dt, name in ((depth, torch.float32, "depth"), (face, torch.int32, "face")):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != verts.device or tuple(t.shape) != (F, H, W):
+            raise ValueError(f"render's {name} must be a {dt} tensor [{F}, {H}, {W}] on the GPU of verts")
+    raster = _raster_handle(verts.device.index, verts.shape[1], faces, (H, W))
+    return raster, depth.detach().contiguous(), face.contiguous()
+
+
+def _edge_weights(raster, verts, intr, depth, face, z_near, cull_backfaces):
+    v, vs, F, _ = _point_set("verts", verts.detach(), None)
+    H, W = face.shape[1], face.shape[2]
+    w = torch.empty((F, H, W, 2), dtype=torch.float32, device=v.device)
+    if F > 0:
+        with torch.cuda.device(v.device):
+            raster.edges_device(v.data_ptr(), vs.frame_stride, F, [float(a) for a in intr], face.data_ptr(), depth.data_ptr(),
+                                w.data_ptr(), z_near=float(z_near), cull_backfaces=cull_backfaces, stream=_stream())
+    return w
+
+
+def edge_weights(verts: torch.Tensor, faces, intr, size, render=None, z_near: float = 0.1, cull_backfaces: bool = False):
+    """The silhouette-edge antialiasing weights of the posed meshes verts [F, V, 3] f32 in an image of size = (height, width):
+    f32 [F, H, W, 2], per pixel p its pair with the right (axis 0) and the lower (axis 1) neighbour q.  w > 0: q receives
+    w (img[p] - img[q]); w < 0: p receives |w| (img[q] - img[p]); 0: no blend; |w| <= 1/2.  render: what render_depth(verts, faces,
+    intr, size, z_near, cull_backfaces) returned, reused; None: rendered here.  The definition (pairs of neighbouring pixels owned
+    by different faces, the bounded walk from the nearer pixel's face to the silhouette edge that crosses the segment between the
+    two centres, the blend by the covered fraction), its tie rules and its error bounds: bodyfit_raster_edges_device,
+    include/bodyfit.h.  NOT differentiable (antialias is).  Runs on torch.cuda.current_stream()."""
+    _check_verts(verts)
+    _check_intr_size(intr, size)
+    raster, depth, face = _render_or(render, verts, faces, intr, size, z_near, cull_backfaces)
+    return _edge_weights(raster, verts, intr, depth, face, float(z_near), bool(cull_backfaces))
+
+
+def _edge_blend(raster, w, image, transpose: bool):
+    F, H, W, C = image.shape
+    out = torch.empty((F, H, W, C), dtype=torch.float32, device=image.device)
+    if F > 0:
+        with torch.cuda.device(image.device):
+            raster.edge_blend_device(w.data_ptr(), image.data_ptr(), C, F, transpose, out.data_ptr(), _stream())
+    return out
+
+
+class _Antialias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, verts, faces, intr, render, z_near, cull_backfaces):
+        F, H, W, C = image.shape
+        raster, depth, face = _render_or(render, verts, faces, intr, (H, W), z_near, cull_backfaces)
+        w = _edge_weights(raster, verts, intr, depth, face, z_near, cull_backfaces)
+        img = image.detach().contiguous()
+        out = _edge_blend(raster, w, img, False)
+        ctx.args = (raster, faces, tuple(float(a) for a in intr), z_near, cull_backfaces)
+        if ctx.needs_input_grad[1]:
+            v, _, _, _ = _point_set("verts", verts.detach(), None)
+            ctx.save_for_backward(w, img, v, depth, face)
+        else:
+            ctx.save_for_backward(w)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        w = ctx.saved_tensors[0]
+        raster, faces, intr, z_near, cull = ctx.args
+        g = g.to(torch.float32).contiguous()
+        g_image = _edge_blend(raster, w, g, True) if ctx.needs_input_grad[0] else None
+        gv = None
+        if ctx.needs_input_grad[1]:
+            _, img, v, depth, face = ctx.saved_tensors
+            v, vs, F, _ = _point_set("verts", v, None)
+            gv = _grad_like(v, vs)
+            dev = v.device
+            C = g.shape[-1]
+            # the blended pairs, frame after frame and ascending inside a frame: code = 2 pixel + axis
+            frame, code = torch.nonzero(w.reshape(F, -1), as_tuple=True)
+            N = int(code.shape[0])
+            if N == 0 or v.shape[1] == 0:
+                gv.zero_()
+            else:
+                pair = code.to(torch.int32).contiguous()
+                offset = torch.zeros(F + 1, dtype=torch.int32, device=dev)
+                offset[1:] = torch.bincount(frame, minlength=F).cumsum(0).to(torch.int32)
+                index = torch.empty(2 * N, dtype=torch.int32, device=dev)
+                bary = torch.empty((2 * N, 3), dtype=torch.float32, device=dev)
+                coef = torch.empty(2 * N, dtype=torch.float32, device=dev)
+                direction = torch.empty((2 * N, 3), dtype=torch.float32, device=dev)
+                offset2 = (2 * offset).contiguous()
+                surface = _surface_handle(dev.index, v.shape[1], faces)
+                rows = api.PointSet.ragged(index.data_ptr(), offset2.data_ptr())     # (the frame structure; its xyz is never read)
+                with torch.cuda.device(dev):
+                    raster.edge_rows_device(v.data_ptr(), vs.frame_stride, F, intr, face.data_ptr(), depth.data_ptr(), img.data_ptr(),
+                                            g.data_ptr(), C, pair.data_ptr(), offset.data_ptr(), N, index.data_ptr(), bary.data_ptr(),
+                                            coef.data_ptr(), direction.data_ptr(), z_near=z_near, cull_backfaces=cull, stream=_stream())
+                    surface.rows_vjp_device(rows, F, 2 * N, index.data_ptr(), bary.data_ptr(), coef.data_ptr(), direction.data_ptr(),
+                                            gv.data_ptr(), vs.frame_stride, _stream())
+        return g_image, gv, None, None, None, None, None
+
+
+def antialias(image: torch.Tensor, verts: torch.Tensor, faces, intr, render=None, z_near: float = 0.1,
+              cull_backfaces: bool = False) -> torch.Tensor:
+    """image ([F, H, W, C] or [F, H, W] f32 on the GPU, C in 1 .. 4: a render_attributes image, a coverage mask as 0 / 1) with the
+    silhouette edges of the posed meshes verts [F, V, 3] f32 antialiased (Laine et al. 2020): an image of the same shape in which a
+    pixel next to an occlusion boundary is blended with its neighbour across the boundary by the fraction of the segment between
+    the two centres that the nearer face's silhouette edge cuts off.  render: what render_depth(verts, faces, intr, (H, W), z_near,
+    cull_backfaces) returned, reused; None: rendered here (one 8-byte read-back).
+
+    Differentiable in image (the blend's exact adjoint, bodyfit_raster_edge_blend_device with transpose) and in verts THROUGH
+    COVERAGE at the fixed face image: the blend weight is a smooth function of the two vertices of the silhouette edge, and
+    loss(antialias(render(verts))).backward() reaches verts.  Gradients of the interpolation inside a face (how image itself changes
+    as its face's corners move) are NOT part of it: pass an image that already carries those if it has them.  The backward: nonzero
+    of the weights lists the blended pairs in ascending order (one host synchronisation), bodyfit_raster_edge_rows_device writes two
+    rows per pair, bodyfit_surface_rows_vjp_device sums them into the vertices: no float atomics, bit-identical from run to run.
+    The definition, its tie rules and error bounds: include/bodyfit.h.  Runs on torch.cuda.current_stream()."""
+    _check_verts(verts)
+    if len(intr) != 4:
+        raise ValueError("intr is (fx, fy, cx, cy)")
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or not image.is_cuda:
+        raise TypeError("image must be a float32 tensor on the GPU")
+    if image.device != verts.device:
+        raise ValueError("image and verts must be on the same GPU")
+    flat = image.ndim == 3
+    img = image.unsqueeze(-1) if flat else image
+    if img.ndim != 4 or img.shape[0] != verts.shape[0] or not 1 <= img.shape[3] <= 4 or img.shape[1] < 1 or img.shape[2] < 1:
+        raise ValueError(f"image must be [F, H, W] or [F, H, W, C] with F = {verts.shape[0]} and C in 1 .. 4, got {tuple(image.shape)}")
+    if not z_near > 0.0:
+        raise ValueError("z_near must be positive")
+    out = _Antialias.apply(img, verts, faces, intr, render, float(z_near), bool(cull_backfaces))
+    return out.squeeze(-1) if flat else out
+
+
+class CoverageTerm(torch.nn.Module):
+    """The EXACT-outline counterpart of SilhouetteTerm: sum over the pixels of (antialias(covered) - mask)^2, in pixel^2.
+
+    mask: [F, H, W] bool / uint8 / float32 on the GPU (a person mask, as 0 / 1; a float mask may hold fractions); intr = (fx, fy, cx,
+    cy).  term(verts), verts [F, V, 3] f32, renders the mesh at the mask's size, takes its coverage {face >= 0} as a 0 / 1 f32 image,
+    antialiases it (antialias, with that render) and returns the f64 sum of squared differences to the mask.  Its gradient reaches
+    verts through the antialiased outline only, so it is non-zero only where the model's outline is within a pixel of a
+    disagreement with the mask: SilhouetteTerm (distance transforms: a pull from any distance) brings the fit there, this term
+    finishes it.  No normal equations are built for it."""
+
+    def __init__(self, mask: torch.Tensor, intr, faces, z_near: float = 0.1, cull_backfaces: bool = False):
+        super().__init__()
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8, torch.float32) or not mask.is_cuda:
+            raise TypeError("mask must be a bool, uint8 or float32 tensor [F, H, W] on the GPU")
+        if mask.ndim != 3 or mask.shape[1] < 1 or mask.shape[2] < 1:
+            raise ValueError(f"mask must be [F, H, W] with H, W >= 1, got {tuple(mask.shape)}")
+        if len(intr) != 4:
+            raise ValueError("intr is (fx, fy, cx, cy)")
+        if not z_near > 0.0:
+            raise ValueError("z_near must be positive")
+        self.intr = tuple(float(a) for a in intr)
+        self.size, self.z_near, self.cull_backfaces = (int(mask.shape[1]), int(mask.shape[2])), float(z_near), bool(cull_backfaces)
+        self.faces = _host_faces(faces).copy()
+        m = mask.detach()
+        self.register_buffer("mask", (m if m.dtype == torch.float32 else (m != 0).to(torch.float32)).contiguous())
+
+    def evaluate(self, verts: torch.Tensor) -> dict:
+        """term(verts) with what it was built from: cost (f64, with the gradient), the render (depth, face) and the antialiased
+        coverage [F, H, W] f32"""
+        _check_verts(verts)
+        if self.mask.device != verts.device or self.mask.shape[0] != verts.shape[0]:
+            raise ValueError(f"the mask has {self.mask.shape[0]} frames on {self.mask.device}, verts has {verts.shape[0]} on {verts.device}")
+        _, depth, face, _ = _render(verts, self.faces, self.intr, self.size, self.z_near, self.cull_backfaces, False)
+        covered = (face >= 0).to(torch.float32)
+        soft = antialias(covered, verts, self.faces, self.intr, render=(depth, face), z_near=self.z_near,
+                         cull_backfaces=self.cull_backfaces)
+        cost = (soft.double() - self.mask.double()).square().sum()
+        return {"cost": cost, "depth": depth, "face": face, "coverage": soft}
+
+    def forward(self, verts: torch.Tensor) -> torch.Tensor:
+        return self.evaluate(verts)["cost"]
 
 
 _NO_FACES = np.zeros((0, 3), np.int32)

@@ -878,7 +878,7 @@ int bodyfit_overlay_last_timing(bodyfit_overlay* ov, float ms[4]);
  * A bodyfit_raster holds one topology (faces: host int32 [n_faces][3], ids in [0, n_verts), else BODYFIT_ERR_INVALID; n_faces =
  * 0 is accepted) and one image size (1 .. 16384 each way) on one device, and the workspace of its calls, which grows on demand
  * (96 bytes per (frame, face), 12 per (frame, tile of 32 x 8 pixels), 4 per (face, tile) pair; 8 per pixel of the frames of a
- * distance transform).                                                                                                        */
+ * distance transform), and 12 bytes per face of edge neighbours for the antialiasing calls.                                                                                                     */
 typedef struct bodyfit_raster bodyfit_raster;
 int bodyfit_raster_create(int device, int n_verts, int n_faces, const int32_t* faces, int width, int height,
                           bodyfit_raster** out);
@@ -1134,6 +1134,101 @@ int bodyfit_raster_sample_device(bodyfit_raster* r, const float* d_points, long 
                                  int image_kind, int n_channels, long long image_frame_stride,
                                  const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
                                  float* d_grad /* may be NULL */, void* stream);
+/* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster.hip): the coverage of a render as a smooth
+ * function of the vertices, after Laine et al., "Modular Primitives for High-Performance Differentiable Rendering" (2020).  Only
+ * COVERAGE carries a gradient here: how an attribute interpolates inside a face as its corners move is not part of it.
+ * The handle keeps, per (face, edge e = corners e, (e + 1) % 3), the lowest-id OTHER face of the topology that holds both vertex ids
+ * of the edge, -1 if none (or if the two ids are equal): 12 bytes per face, built by bodyfit_raster_create on the host.
+ * DEFINITION, per frame, exact from the f32 vertices, the f64 intrinsics, z_near and cull_backfaces (projection and "drawn" are
+ * those of bodyfit_raster_render_device), the images d_face int32 and d_depth f32 [H][W] of a render (a face value outside
+ * [0, n_faces) is empty: it counts as -1 with depth +inf) and an image img f32 [H][W][C], C in 1 .. 4.
+ * PAIRS.  Pixel p = (i, j) forms a pair with its right neighbour q = (i, j + 1) (axis 0) and with its lower neighbour q = (i + 1, j)
+ * (axis 1).  A pair is a CANDIDATE iff face[p] != face[q].  The near pixel n is p if depth[p] <= depth[q], else q; o is the other;
+ * t = face[n].  If t is empty or not drawn in this frame the pair does not blend.
+ * CROSSING.  Axis 0: the scanline is y0 = i, the segment x in [j, j + 1], "along" is u and "across" is v; axis 1: y0 = j, the segment
+ * v in [i, i + 1], along is v and across is u (exchange u and v throughout).  Written for axis 0, an edge (a, b) of a face CROSSES iff
+ * exactly one of  v_a - y0 <= 0 < v_b - y0  and  v_b - y0 <= 0 < v_a - y0  holds (half-open: a vertex on the scanline counts once) and
+ *   x* = u_a + (u_b - u_a) s,   s = (y0 - v_a) / (v_b - v_a),   lies in [j, j + 1], both ends included;   d = |x* - x_n|,
+ * x_n the near pixel's centre on the segment (j or j + 1).
+ * WALK.  Start in t with no entry edge; at most BODYFIT_AA_WALK = 8 steps (faces visited).  In each step: among the current face's
+ * crossing edges other than its entry edge take the one of least d, ties to the lowest edge index; none: the pair does not blend.
+ * Let t' be the table's face for that (face, edge).  The edge is a SILHOUETTE EDGE if t' does not exist, or t' is not drawn in this
+ * frame (the cull flag counts), or t' is FOLDED over the current face: with side(x) = (u_b - u_a)(v_x - v_a) - (v_b - v_a)(u_x - u_a)
+ * and c, c' the corners of the current face and of t' that are not on the edge, side(c) side(c') >= 0.  A silhouette edge ends the
+ * walk: the pair BLENDS with (face, edge, s, x*, d).  Otherwise the walk steps into t' and the edge, identified by its two vertex ids,
+ * becomes the entry edge.  Eight steps without a silhouette edge: the pair does not blend.  (Faces along a smooth silhouette are seen
+ * edge-on and are thinner than a pixel: the face under the pixel centre is usually not the one that holds the silhouette edge, so the
+ * walk is part of the definition.  On the two-sphere scene of the tests one face finds 120 of 242 body / background pairs, eight all.)
+ * BLEND.  d >= 1/2: o receives alpha = d - 1/2 of (img[n] - img[o]); else n receives alpha = 1/2 - d of (img[o] - img[n]).
+ * out[p] = img[p] + what p receives from its at most four pairs, taken in the order left, right, up, down.
+ * WEIGHT IMAGE d_weight f32 [H][W][2], one entry per (pixel p, axis); a pair that would leave the image holds 0.  w > 0: q receives
+ * w (img[p] - img[q]); w < 0: p receives |w| (img[q] - img[p]); w = 0: no blend.  |w| <= 1/2 always.
+ * GRADIENT at the fixed images and walk.  With r the receiver and sigma = +1 if n = p, else -1:
+ *   G = dL/dx* = sigma sum_c g[r][c] (img[n][c] - img[o][c]);
+ * for axis 0, k = (u_b - u_a) / (v_b - v_a):  d(x*) / d(u_a, v_a) = (1 - s)(1, -k),  d(x*) / d(u_b, v_b) = s (1, -k);  with grad u = (fx / Z, 0,
+ * -fx X / Z^2) and grad v = (0, fy / Z, -fy Y / Z^2) a blended pair is TWO rows of bodyfit_surface_rows_vjp_device:
+ *   index = the walk's final face,  bary = one-hot at corner a | b,  coef = G (1 - s) | G s,  dir = m_a | m_b,  m = grad u - k grad v
+ * at that corner (axis 1: m = grad v - k grad u, k = (v_b - v_a) / (u_b - u_a)).  The gradient in img is the blend's exact adjoint.
+ * CONTRACT.  Every deciding operation is f64 and unfused, in this order: the projection of k_rs_faces; da = v_a - y0, db = v_b - y0;
+ * den = v_b - v_a; s = (y0 - v_a) / den; x* = u_a + (u_b - u_a) s; d = |x* - x_n|; k = (u_b - u_a) / den; side as written above, the
+ * fold test on the two signs; alpha = d - 1/2 or 1/2 - d.  Only stores round to f32.  No float atomics.  A frame's result depends on
+ * that frame only: bit-identical from run to run and whatever n_frames.
+ * BANDS, eps = 2^-53, P = P_t of the render's contract for the face at hand (for the fold test the larger of the two faces'), K =
+ * |u_b - u_a| / |v_b - v_a| of the edge, k_c = 8, k_x = 32.  A decision is SURE when its quantity clears its band:
+ *   area (drawn, culled):  |A| > 2^-46 P^2, the render's;      straddle:  |v_a - y0| >= tau_c = k_c eps P,  and v_b alike;
+ *   inside the segment:  |x* - j|, |x* - (j + 1)| >= tau_x = k_x eps P (1 + K);    least d:  |d - d'| >= tau_x + tau_x';
+ *   fold:  |side(c)|, |side(c')| >= 2^-46 P^2;             receiver:  |d - 1/2| >= tau_x;
+ * and a decision whose f64 evaluation in the stated order is EXACT (it reproduces the exact value: every intermediate representable,
+ * as on scenes with dyadic projections) is sure whatever its margin: the tie rules above then hold to the bit.  A candidate pair all
+ * of whose decisions along the exact walk are sure is DECIDED.  For a decided pair, with w* the exact weight and u = 2^-24:
+ *   |w - w*| <= u |w*| + 2 tau_x                                  (tau_x of the silhouette edge),
+ * and for every pixel, with out* the exact blend of img by the RETURNED weights, T = |img[p]| + sum |w| |img[other] - img[p]| over the
+ * amounts p receives, and k_b = 2:   |out - out*| <= k_b u T   (the adjoint alike, T = |g[p]| + sum |w| |g[p] or g[other]|); against the
+ * exact weights add sum |w - w*| |img[other] - img[p]|.  A row pair of a decided pair, with k_r = 2, T_G = sum_c |g[r][c]| |img[n][c] -
+ * img[o][c]|, tau_s = k_x eps P / |v_b - v_a|, tau_k = tau_s (1 + K), and M_c = |grad along|_c + |k| |grad across|_c at the corner:
+ *   |coef - coef*| <= k_r u |coef*| + |G| tau_s + 2^-48 T_G,        |dir_c - dir*_c| <= k_r u M_c + tau_k |grad across|_c.
+ * Derivation.  A projected coordinate is off by 3 eps P and a (coordinate - integer) by 4 eps P (the render's derivation): below tau_c.
+ * den: two coordinates and a rounding, 8 eps P.  s in [0, 1]: (4 + 8 s) eps P / |den| + eps <= 13 eps P / |den|.  x*: 3 eps P from u_a,
+ * 8 eps P s from u_b - u_a, |u_b - u_a| ds = 13 eps P K, the product's and the sum's roundings 3 eps P: below eps P (14 + 13 K) <= tau_x / 2;
+ * x* - x_n and alpha round once each (2 eps) and the store once (u |w|), which gives the bound on w with room for the terms of second
+ * order.  side: factors off by 8 eps P against partners <= 2 P, two products and a difference of numbers <= 4 P^2: 80 eps P^2 < 2^-46
+ * P^2, as the render's area.  The blend: a difference of f32 in f64 (1 eps), a product, at most four sums: 7 eps T, and the store's u:
+ * k_b = 2.  G: C products and sums, (C + 2) eps T_G <= 2^-50 T_G; (1 - s) and s carry ds <= tau_s / 2; the store u |coef|: k_r = 2.  k:
+ * 8 eps P (1 + K) / |den| + eps K <= tau_k / 2; grad u, grad v: four roundings each, the store's u.
+ * Shape: one thread per pixel, neighbouring lanes on neighbouring columns; equal ids cost two compares and one 8-byte store; only a
+ * candidate pair gathers vertices and walks (a few per cent of the lanes).  Pairs across the render's tile borders are ordinary pairs.
+ * bodyfit_raster_edges_device: d_verts as for the render, d_face / d_depth [n_frames][H][W] dense, d_weight f32 [n_frames][H][W][2]
+ * dense, 8-byte aligned (it is read and written as pairs); every element is written, whatever it held.  Asynchronous on `stream`, no
+ * host synchronisation, no workspace.  n_frames == 0:
+ * a successful no-op; n_faces == 0: every weight 0.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames, z_near
+ * <= 0 or NaN, fx or fy <= 0 or a non-finite intrinsic, and with frames to write: NULL d_weight, NULL d_verts / d_face / d_depth
+ * (n_faces > 0), a stride below 3 n_verts, 2^39 pixels or more.                                                                   */
+#define BODYFIT_AA_WALK 8
+int bodyfit_raster_edges_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames, double fx,
+                                double fy, double cx, double cy, float z_near, int cull_backfaces, const int32_t* d_face,
+                                const float* d_depth, float* d_weight, void* stream);
+/* The blend of d_image f32 [n_frames][H][W][n_channels] by d_weight (as above), or with transpose != 0 its exact adjoint (d_image is
+ * then the upstream gradient): d_out of the same shape, every element written; d_out must not be d_image.  One thread per pixel: it
+ * gathers its four weights and neighbours and stores n_channels floats.  The topology is not used.  Asynchronous on `stream`.
+ * n_frames == 0: a no-op.  BODYFIT_ERR_INVALID: NULL handle, negative n_frames, n_channels outside 1 .. 4, and with frames to write a
+ * NULL d_weight / d_image / d_out, d_out == d_image, 2^39 pixels or more.                                                        */
+int bodyfit_raster_edge_blend_device(bodyfit_raster* r, const float* d_weight, const float* d_image, int n_channels, int n_frames,
+                                     int transpose, float* d_out, void* stream);
+/* The ROWS of listed pairs (k_rs_edge_rows): d_pair int32 [N] = 2 (i W + j) + axis inside the pair's frame, d_offset int32
+ * [n_frames + 1] the ragged convention of the depth rows, or NULL: N / n_frames pairs per frame.  d_image and d_grad f32
+ * [n_frames][H][W][n_channels]: the blended image's input and the upstream gradient of its output.  The kernel repeats the walk and
+ * writes rows 2 n (corner a) and 2 n + 1 (corner b) of pair n: d_index int32 [2 N], d_bary f32 [2 N][3], d_coef f32 [2 N], d_dir f32
+ * [2 N][3]; a listed pair that does not blend (or lies outside the image) gets index -1, bary = dir = 0 and coef = 0.  Every row is
+ * written.  The rows' frame structure for bodyfit_surface_rows_vjp_device is 2 d_offset.  Asynchronous on `stream`, no workspace.
+ * n_frames == 0 or N == 0: a no-op; n_faces == 0: every row void.  BODYFIT_ERR_INVALID: NULL handle, negative counts, n_channels
+ * outside 1 .. 4, z_near <= 0 or NaN, fx or fy <= 0 or a non-finite intrinsic, pairs without frames, a uniform N that n_frames does not
+ * divide, 2^30 pairs or pixels of a frame or more, and with rows to write: NULL d_pair or output, NULL d_verts / d_face / d_depth /
+ * d_image / d_grad (n_faces > 0), a stride below 3 n_verts.                                                                      */
+int bodyfit_raster_edge_rows_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames, double fx,
+                                    double fy, double cx, double cy, float z_near, int cull_backfaces, const int32_t* d_face,
+                                    const float* d_depth, const float* d_image, const float* d_grad, int n_channels,
+                                    const int32_t* d_pair, const int32_t* d_offset /* may be NULL */, long long n_pairs,
+                                    int32_t* d_index, float* d_bary, float* d_coef, float* d_dir, void* stream);
 /* Statistics of the handle's latest render (from its read-back; no synchronisation): the (face, tile) pairs binned, and the
  * longest tile list.                                                                                                          */
 int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
