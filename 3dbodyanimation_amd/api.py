@@ -280,6 +280,10 @@ def load_library():
     lib.bodyfit_raster_depth_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
                                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_interp_rows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                                                      C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]
     lib.bodyfit_raster_shade_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
@@ -1049,6 +1053,24 @@ class Raster:
                                                                float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
                                                                d_face_image_ptr, d_pixel_ptr, d_offset_ptr, int(n_rows),
                                                                d_index_ptr, d_z_ptr, d_bary_ptr, d_dir_ptr, stream))
+
+    def interp_rows_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, intr, d_face_image_ptr: int,
+                           d_pixel_ptr: int | None, d_offset_ptr: int | None, n_rows: int, d_attr_ptr: int | None,
+                           attr_frame_stride: int, n_channels: int, d_grad_image_ptr: int | None, d_grad_z_ptr: int | None,
+                           d_index_ptr: int, d_bary_ptr: int | None = None, d_dir_ptr: int | None = None,
+                           d_value_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_raster_interp_rows_device: per row (addressed as in depth_rows_device) the face (index [N] int32, -1: void), the
+        object-space barycentrics bary [N, 3] f32 and the ONE direction dir [N, 3] f32 with dL/dcorner_a = bary_a dir, for the
+        upstream gradients grad_image [F, H, W, n_channels] f32 in the attributes (rows of n_channels f32 per vertex, 0 .. 4;
+        attr_frame_stride floats between frames, 0: shared) interpolated over the face and grad_z [F, H, W] f32 (or None) in the
+        ray-plane depth, both read at the row's pixel; value [N, n_channels] f32 or None: the interpolated attributes.
+        n_channels = 0 (attr and grad_image None) is the depth-only case.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_interp_rows_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                                float(intr[0]), float(intr[1]), float(intr[2]), float(intr[3]),
+                                                                d_face_image_ptr, d_pixel_ptr, d_offset_ptr, int(n_rows),
+                                                                d_attr_ptr, int(attr_frame_stride), int(n_channels),
+                                                                d_grad_image_ptr, d_grad_z_ptr, d_index_ptr, d_bary_ptr,
+                                                                d_dir_ptr, d_value_ptr, stream))
 
     def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_frame_stride: int, n_frames: int, invert: bool,
                         d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):

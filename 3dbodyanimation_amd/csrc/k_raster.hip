@@ -16,6 +16,9 @@
 //   k_rs_depth_rows one thread per depth row (a pixel of a frame): the ray through the pixel against the plane of the face the
 //                face-id image holds there: z, the object-space barycentrics and the direction m with dz/dcorner_a = beta_a m
 //                (bodyfit_raster_depth_rows_device), f64 throughout, plain stores
+//   k_rs_interp_rows<C> one thread per interpolation row: the depth row's face, ray and beta, and the one direction dir with
+//                dL/dcorner_c = beta_c dir for upstream gradients in the interpolated attributes and in z
+//                (bodyfit_raster_interp_rows_device), f64 throughout, plain stores
 //   k_rs_shade<C>  one thread per pixel of a render: per-vertex attributes interpolated with the perspective-correct weights
 //                (lambda_a / Z_a) / sum, the background where the pixel is void (bodyfit_raster_shade_device)
 //   k_rs_sample<C, T>  one thread per (frame, point): the point's projection, the bilinear value of a u8 or f32 image there and
@@ -290,6 +293,112 @@ __global__ __launch_bounds__(256) void k_rs_depth_rows(const float* __restrict__
     for (int a = 0; a < 3; ++a) bary[3 * (size_t)row + a] = ok ? (float)b[a] : 0.0f;
   if (dir)
     for (int a = 0; a < 3; ++a) dir[3 * (size_t)row + a] = ok ? (float)m[a] : 0.0f;
+}
+
+// One thread per interpolation row: the depth row's evaluation, operation for operation (so index and beta are the depth rows'
+// bits), then the ONE direction that carries dL/dz and dL/dimage to the three corners, dL/dv_c = beta_c dir (include/bodyfit.h,
+// INTERPOLATION ROWS).  f64 and unfused, in the order the header counts and tests/interp_ref.py restates:
+//   s_a = ((G_0 A_a0 + G_1 A_a1) + G_2 A_a2) + G_3 A_a3 (the products of two f32 are exact in f64), p = s_1 - s_0, q = s_2 - s_0,
+//   E = q e1 - p e2 (= sum_a s_a (v_c - v_b): the DIFFERENCES against s_0, so three equal s_a give an exact 0),
+//   w = (n x E) (1 / (n . n)) (= sum_a s_a g_a),  k = (w_x d_x + w_y d_y) + w_z,  a = w - k m (= sum_a s_a h_a),
+//   dir = g_z m - a,  value_c = (beta_0 A_0c + beta_1 A_1c) + beta_2 A_2c from the unrounded beta.
+// C = 0: no attributes, dir = g_z m.  The row reads the upstream gradients at its own (frame, pixel): nothing is gathered before
+// the call.  Only the stores round to f32.
+template <int C>
+__global__ __launch_bounds__(256) void k_rs_interp_rows(const float* __restrict__ verts, long long frame_stride,
+                                                        const int* __restrict__ faces, int nF, int F, int W, int H, double fx,
+                                                        double fy, double cx, double cy, const int* __restrict__ face_img,
+                                                        const int* __restrict__ pixel, const int* __restrict__ offset,
+                                                        long long per_frame, long long n_rows, const float* __restrict__ attr,
+                                                        long long attr_stride, const float* __restrict__ grad_image,
+                                                        const float* __restrict__ grad_z, int* __restrict__ index,
+                                                        float* __restrict__ bary, float* __restrict__ dir,
+                                                        float* __restrict__ value) {
+  const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n_rows) return;
+  const long long ppf = (long long)W * H;
+  long long frame, pix;
+  if (pixel) {
+    frame = offset ? rs_frame_of(offset, F, row) : row / per_frame;
+    pix = pixel[row];
+  } else {
+    frame = row / ppf;
+    pix = row - frame * ppf;
+  }
+  int f = -1;
+  if (pix >= 0 && pix < ppf) f = face_img[(size_t)frame * (size_t)ppf + (size_t)pix];
+  bool ok = (unsigned)f < (unsigned)nF;     // empty (-1), not a face of this topology, or a pixel outside the image
+  double b[3] = {0.0, 0.0, 0.0}, r[3] = {0.0, 0.0, 0.0};
+  double val[C > 0 ? C : 1] = {};
+  if (ok) {
+    const float* c = verts + (size_t)frame * (size_t)frame_stride;
+    size_t id[3];
+    double v[3][3];
+    for (int k = 0; k < 3; ++k) {
+      id[k] = (size_t)faces[3 * f + k];
+      for (int a = 0; a < 3; ++a) {
+        const float X = c[3 * id[k] + a];
+        if (!(X - X == 0.0f)) ok = false;   // (a NaN fails every comparison; X - X is NaN for an infinity)
+        v[k][a] = (double)X;
+      }
+    }
+    const double e1x = v[1][0] - v[0][0], e1y = v[1][1] - v[0][1], e1z = v[1][2] - v[0][2];
+    const double e2x = v[2][0] - v[0][0], e2y = v[2][1] - v[0][1], e2z = v[2][2] - v[0][2];
+    const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    const long long i = pix / W, j = pix - i * W;
+    const double dx = ((double)j - cx) / fx, dy = ((double)i - cy) / fy;
+    const double D = (nx * dx + ny * dy) + nz;
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    if (!(nn > 0.0) || !(D != 0.0)) ok = false;
+    if (ok) {
+      const double N0 = (nx * v[0][0] + ny * v[0][1]) + nz * v[0][2];
+      const double zz = N0 / D;
+      const double x[3] = {zz * dx, zz * dy, zz};
+      const double inv_nn = 1.0 / nn;
+      for (int a = 0; a < 3; ++a) {
+        const double* vb = v[(a + 1) % 3];
+        const double* vc = v[(a + 2) % 3];
+        const double px = vb[0] - x[0], py = vb[1] - x[1], pz = vb[2] - x[2];
+        const double qx = vc[0] - x[0], qy = vc[1] - x[1], qz = vc[2] - x[2];
+        const double wx = py * qz - pz * qy, wy = pz * qx - px * qz, wz = px * qy - py * qx;
+        b[a] = ((nx * wx + ny * wy) + nz * wz) * inv_nn;
+      }
+      const double m[3] = {nx / D, ny / D, nz / D};
+      const size_t at = (size_t)frame * (size_t)ppf + (size_t)pix;
+      if (grad_z) {
+        const double gz = (double)grad_z[at];
+        for (int a = 0; a < 3; ++a) r[a] = gz * m[a];
+      }
+      if (C > 0) {
+        const float* A = attr + (size_t)frame * (size_t)attr_stride;
+        double s[3];
+        for (int k = 0; k < 3; ++k) {
+          double acc = 0.0;
+          for (int ch = 0; ch < C; ++ch) {
+            const double Ak = (double)A[C * id[k] + ch];
+            const double t = (double)grad_image[C * at + ch] * Ak;
+            acc = ch == 0 ? t : acc + t;
+            const double bt = b[k] * Ak;
+            val[ch] = k == 0 ? bt : val[ch] + bt;
+          }
+          s[k] = acc;
+        }
+        const double p = s[1] - s[0], q = s[2] - s[0];
+        const double Ex = q * e1x - p * e2x, Ey = q * e1y - p * e2y, Ez = q * e1z - p * e2z;
+        const double wx = (ny * Ez - nz * Ey) * inv_nn, wy = (nz * Ex - nx * Ez) * inv_nn, wz = (nx * Ey - ny * Ex) * inv_nn;
+        const double kk = (wx * dx + wy * dy) + wz;
+        const double a3[3] = {wx - kk * m[0], wy - kk * m[1], wz - kk * m[2]};
+        for (int a = 0; a < 3; ++a) r[a] = grad_z ? r[a] - a3[a] : -a3[a];
+      }
+    }
+  }
+  index[row] = ok ? f : -1;
+  if (bary)
+    for (int a = 0; a < 3; ++a) bary[3 * (size_t)row + a] = ok ? (float)b[a] : 0.0f;
+  if (dir)
+    for (int a = 0; a < 3; ++a) dir[3 * (size_t)row + a] = ok ? (float)r[a] : 0.0f;
+  if (C > 0 && value)
+    for (int ch = 0; ch < C; ++ch) value[C * (size_t)row + ch] = ok ? (float)val[ch] : 0.0f;
 }
 
 // One thread per pixel, neighbouring lanes on neighbouring columns: the face's three ids, the three Z and the 3 C attributes are
@@ -858,6 +967,52 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
   BODYFIT_LAUNCH(k_rs_depth_rows, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, d_verts, verts_frame_stride,
                  r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy, cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames,
                  n_rows, d_index, d_z, d_bary, d_dir);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_interp_rows_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                      double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                      const int32_t* d_pixel, const int32_t* d_offset, long long n_rows, const float* d_attr,
+                                      long long attr_frame_stride, int n_channels, const float* d_grad_image,
+                                      const float* d_grad_z, int32_t* d_index, float* d_bary, float* d_dir, float* d_value,
+                                      void* stream) {
+  const char* fn = "bodyfit_raster_interp_rows_device";
+  if (!r) return rs_invalid(fn, "handle is NULL");
+  if (n_frames < 0 || n_rows < 0) return rs_invalid(fn, "negative n_frames or n_rows");
+  if (!(fx > 0.0 && fy > 0.0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)))
+    return rs_invalid(fn, "fx and fy must be positive, and the intrinsics finite");
+  if (n_channels < 0 || n_channels > 4) return rs_invalid(fn, "n_channels outside 0 .. 4");
+  if (d_offset && !d_pixel) return rs_invalid(fn, "d_offset without d_pixel");
+  const long long ppf = (long long)r->W * r->H;
+  if (!d_pixel && n_rows != ppf * n_frames) return rs_invalid(fn, "without d_pixel n_rows must be n_frames H W");
+  if (n_rows >= (1ll << 31) - 4096) return rs_invalid(fn, "2^31 rows or more in one call");
+  if (n_rows > 0 && n_frames == 0) return rs_invalid(fn, "rows without frames");
+  if (d_pixel && !d_offset && n_frames > 0 && n_rows % n_frames != 0)
+    return rs_invalid(fn, "a uniform row set needs n_rows divisible by n_frames");
+  if (n_frames == 0 || n_rows == 0) return BODYFIT_OK;
+  if (!d_face_image || !d_index) return rs_invalid(fn, "d_face_image or d_index is NULL");
+  if (r->nF > 0 && !d_verts) return rs_invalid(fn, "d_verts is NULL");
+  if (verts_frame_stride < 3ll * r->nV) return rs_invalid(fn, "verts_frame_stride below 3 n_verts");
+  if (n_channels > 0 && (!d_attr || !d_grad_image)) return rs_invalid(fn, "d_attr or d_grad_image is NULL with n_channels > 0");
+  if (n_channels > 0 && attr_frame_stride != 0 && attr_frame_stride < (long long)n_channels * r->nV)
+    return rs_invalid(fn, "a non-zero attr_frame_stride below n_channels n_verts");
+  if (n_channels == 0 && !d_grad_z) return rs_invalid(fn, "n_channels == 0 needs d_grad_z");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((n_rows + 255) / 256));
+  auto launch = [&](auto kernel) {
+    BODYFIT_LAUNCH(kernel, grid, dim3(256), 0, st, d_verts, verts_frame_stride, r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy,
+                   cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames, n_rows, d_attr, attr_frame_stride, d_grad_image,
+                   d_grad_z, d_index, d_bary, d_dir, d_value);
+  };
+  switch (n_channels) {
+    case 0: launch(k_rs_interp_rows<0>); break;
+    case 1: launch(k_rs_interp_rows<1>); break;
+    case 2: launch(k_rs_interp_rows<2>); break;
+    case 3: launch(k_rs_interp_rows<3>); break;
+    default: launch(k_rs_interp_rows<4>); break;
+  }
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

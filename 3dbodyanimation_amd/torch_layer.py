@@ -115,8 +115,16 @@ differentiable in the vertices and in the colours.
 Every render above is piecewise constant in the vertices.  antialias is bodyfit_raster_edges_device (k_raster.hip: per pair of
 neighbouring pixels owned by different faces, a bounded walk to the nearer face's silhouette edge and the fraction of the segment
 between the two centres it cuts off) followed by bodyfit_raster_edge_blend_device; its backward is that blend transposed for the
-image and, for the vertices, bodyfit_raster_edge_rows_device into bodyfit_surface_rows_vjp_device.  Only coverage carries a
-gradient: the interpolation inside a face does not.  CoverageTerm is the exact-outline counterpart of SilhouetteTerm.
+image and, for the vertices, bodyfit_raster_edge_rows_device into bodyfit_surface_rows_vjp_device.  Of antialias only coverage
+carries a gradient: the interpolation inside a face does not.  CoverageTerm is the exact-outline counterpart of SilhouetteTerm.
+
+    image, face = render_attributes(verts, faces, intr, (H, W), colours, interior=True)   # ALSO differentiable in verts, inside the faces
+    term = RenderedPhotometricTerm(video, intr, faces, trunc=30.0)       # sum rho(|antialias(render) - I|^2) over the pixels
+
+interior=True adds the middle of rasterize -> interpolate -> antialias: the same image, and in the backward one row per shaded
+pixel from bodyfit_raster_interp_rows_device (k_raster.hip: the object-space barycentrics of the pixel's ray in its face and the
+one direction that carries dL/dimage to the three corners) into bodyfit_surface_rows_vjp_device.  RenderedPhotometricTerm is
+PhotometricTerm at the pixels instead of the vertices: interior and coverage gradients of one render.
 """
 from __future__ import annotations
 
@@ -1766,8 +1774,8 @@ class SilhouetteTerm(torch.nn.Module):
 # ---- vertex colours: attribute render, image sampling, colour fusion and the photometric term -----------------------------------
 class _RenderAttributes(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, attr, verts, faces, intr, size, background, z_near, cull_backfaces):
-        raster, _, face, bary = _render(verts, faces, intr, size, z_near, cull_backfaces, True)
+    def forward(ctx, attr, verts, faces, intr, size, background, z_near, cull_backfaces, interior):
+        raster, depth, face, bary = _render(verts, faces, intr, size, z_near, cull_backfaces, True)
         v, vs, F, _ = _point_set("verts", verts.detach(), None)
         H, W = int(size[0]), int(size[1])
         V, C = v.shape[1], attr.shape[-1]
@@ -1779,36 +1787,80 @@ class _RenderAttributes(torch.autograd.Function):
             with torch.cuda.device(v.device):
                 raster.shade_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, a.data_ptr(),
                                     0 if shared else V * C, C, F, background, image.data_ptr(), weight.data_ptr(), _stream())
-        if ctx.needs_input_grad[0]:
+        ctx.interior = bool(interior) and ctx.needs_input_grad[1]
+        if ctx.needs_input_grad[0] or ctx.interior:
             ctx.rows = (_surface_handle(v.device.index, V, faces), F, V, C, H * W, shared)
-            ctx.save_for_backward(face, weight)
-        ctx.mark_non_differentiable(face)
-        return image, face
+            if ctx.interior:
+                ctx.raster = (raster, vs, tuple(float(x) for x in intr))
+                ctx.save_for_backward(face, weight, v, a)
+            else:
+                ctx.save_for_backward(face, weight)
+        ctx.mark_non_differentiable(face, depth)
+        return image, face, depth
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g_image, _g_face):
-        face, weight = ctx.saved_tensors
+    def backward(ctx, g_image, _g_face, _g_depth):
+        if not (ctx.needs_input_grad[0] or ctx.interior):       # (verts alone asks, without interior: there is nothing to give)
+            return (None,) * 9
+        face, weight = ctx.saved_tensors[:2]
         surface, F, V, C, ppf, shared = ctx.rows
         dev = face.device
-        g = torch.zeros((F, V, C), dtype=torch.float32, device=dev)
-        if g_image is not None and F * V * ppf > 0:
-            N = F * ppf
-            gi = g_image.to(torch.float32).reshape(N, C)
-            coef = torch.ones(N, dtype=torch.float32, device=dev)
-            rows = api.PointSet.uniform(face.data_ptr(), ppf, 3 * ppf)      # (the rows' frame structure; its xyz is never read)
-            for c0 in range(0, C, 3):
-                n = min(3, C - c0)
-                direction = torch.zeros((N, 3), dtype=torch.float32, device=dev)
-                direction[:, :n] = gi[:, c0:c0 + n]
-                gv = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
-                with torch.cuda.device(dev):
-                    surface.rows_vjp_device(rows, F, N, face.data_ptr(), weight.data_ptr(), coef.data_ptr(), direction.data_ptr(),
-                                            gv.data_ptr(), 3 * V, _stream())
-                g[:, :, c0:c0 + n] = gv[:, :, :n]
-        if shared:
-            g = g.double().sum(dim=0).to(torch.float32)
-        return g, None, None, None, None, None, None, None
+        g = None
+        if ctx.needs_input_grad[0]:
+            g = torch.zeros((F, V, C), dtype=torch.float32, device=dev)
+            if g_image is not None and F * V * ppf > 0:
+                N = F * ppf
+                gi = g_image.to(torch.float32).reshape(N, C)
+                coef = torch.ones(N, dtype=torch.float32, device=dev)
+                rows = api.PointSet.uniform(face.data_ptr(), ppf, 3 * ppf)      # (the rows' frame structure; its xyz is never read)
+                for c0 in range(0, C, 3):
+                    n = min(3, C - c0)
+                    direction = torch.zeros((N, 3), dtype=torch.float32, device=dev)
+                    direction[:, :n] = gi[:, c0:c0 + n]
+                    gv = torch.empty((F, V, 3), dtype=torch.float32, device=dev)
+                    with torch.cuda.device(dev):
+                        surface.rows_vjp_device(rows, F, N, face.data_ptr(), weight.data_ptr(), coef.data_ptr(), direction.data_ptr(),
+                                                gv.data_ptr(), 3 * V, _stream())
+                    g[:, :, c0:c0 + n] = gv[:, :, :n]
+            if shared:
+                g = g.double().sum(dim=0).to(torch.float32)
+        g_verts = _interior_backward(ctx, g_image) if ctx.interior else None
+        return g, g_verts, None, None, None, None, None, None, None
+
+
+def _interior_backward(ctx, g_image):
+    """dL/dverts of _RenderAttributes through the interpolation inside the faces, at the fixed face image: the pixels the shade did
+    not void as rows of bodyfit_raster_interp_rows_device, summed by ONE bodyfit_surface_rows_vjp_device call"""
+    face, weight, v, a = ctx.saved_tensors
+    surface, F, V, C, ppf, shared = ctx.rows
+    raster, vs, intr = ctx.raster
+    dev = face.device
+    gv = _grad_like(v, vs)
+    N = 0
+    if g_image is not None and F * V * ppf > 0:
+        # the shaded pixels (their weights are >= 0 and sum to 1: not all zero), frame after frame and ascending inside a frame
+        frame, pix = torch.nonzero((weight != 0).any(dim=-1).reshape(F, ppf), as_tuple=True)
+        N = int(pix.shape[0])
+    if N == 0:
+        gv.zero_()
+        return gv
+    pixel = pix.to(torch.int32).contiguous()
+    offset = torch.zeros(F + 1, dtype=torch.int32, device=dev)
+    offset[1:] = torch.bincount(frame, minlength=F).cumsum(0).to(torch.int32)
+    gi = g_image.to(torch.float32).contiguous()
+    index = torch.empty(N, dtype=torch.int32, device=dev)
+    bary = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    direction = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    coef = torch.ones(N, dtype=torch.float32, device=dev)
+    rows = api.PointSet.ragged(index.data_ptr(), offset.data_ptr())      # (the rows' frame structure; its xyz is never read)
+    with torch.cuda.device(dev):
+        raster.interp_rows_device(v.data_ptr(), vs.frame_stride, F, intr, face.data_ptr(), pixel.data_ptr(), offset.data_ptr(), N,
+                                  a.data_ptr(), 0 if shared else V * C, C, gi.data_ptr(), None, index.data_ptr(), bary.data_ptr(),
+                                  direction.data_ptr(), None, _stream())
+        surface.rows_vjp_device(rows, F, N, index.data_ptr(), bary.data_ptr(), coef.data_ptr(), direction.data_ptr(),
+                                gv.data_ptr(), vs.frame_stride, _stream())
+    return gv
 
 
 def _check_intr_size(intr, size):
@@ -1838,7 +1890,7 @@ def _check_per_vertex(t, name, F: int, V: int, device):
 
 
 def render_attributes(verts: torch.Tensor, faces, intr, size, attr: torch.Tensor, background=0.0, z_near: float = 0.1,
-                      cull_backfaces: bool = False):
+                      cull_backfaces: bool = False, interior: bool = False):
     """The per-vertex attributes attr ([V, C] shared by the frames, or [F, V, C]; f32, C in 1 .. 4: colours) of the posed meshes
     verts [F, V, 3] f32 as the camera intr sees them in an image of size = (height, width): (image [F, H, W, C] f32, face
     [F, H, W] int32).  render_depth's render (same arguments, same handle, one 8-byte read-back) followed by
@@ -1846,10 +1898,20 @@ def render_attributes(verts: torch.Tensor, faces, intr, size, attr: torch.Tensor
     w_a = (lambda_a / Z_a) / sum, elsewhere background (a float, or C floats).  The definition and its error bound:
     include/bodyfit.h.
 
-    Differentiable in attr ONLY, at the fixed render: NOT differentiable in verts (neither through the weights nor through
-    visibility or coverage; antialias(image, verts, ...) adds the gradient through coverage).  The backward is bodyfit_surface_rows_vjp_device with the pixels as rows (index = the face image,
+    Differentiable in attr at the fixed render, and by default in attr ONLY: NOT differentiable in verts (neither through the
+    weights nor through visibility or coverage; antialias(image, verts, ...) adds the gradient through coverage).  The backward is
+    bodyfit_surface_rows_vjp_device with the pixels as rows (index = the face image,
     bary = the stored weights, coef = 1, direction = the upstream gradient, three channels per call: C = 4 takes two); shared
-    attributes get the frames' gradients summed in f64.  No float atomics, no index_add_: bit-identical from run to run."""
+    attributes get the frames' gradients summed in f64.  No float atomics, no index_add_: bit-identical from run to run.
+
+    interior=True: the same forward, launch for launch and bit for bit, is ALSO differentiable in verts through the interpolation
+    INSIDE the faces, at the fixed face image and the fixed pixel rays: how a pixel's value changes as its face's corners move
+    under it (a print sliding over the chest), which neither the default nor antialias carries.  The backward lists the pixels
+    the shade did not void (one nonzero of its weights: one host synchronisation, as antialias), writes one "barycentric x
+    direction" row per pixel whatever C (bodyfit_raster_interp_rows_device: the object-space barycentrics of the pixel's ray in
+    its face and dir = -sum_a (sum_c G_c attr_a,c) h_a) and sums them into the layout of verts with one
+    bodyfit_surface_rows_vjp_device call.  Not part of it: visibility and coverage (antialias), z_near and culling.  The
+    gradient in attr is the same with and without it."""
     _check_verts(verts)
     _check_intr_size(intr, size)
     _check_per_vertex(attr, "attr", verts.shape[0], verts.shape[1], verts.device)
@@ -1857,7 +1919,8 @@ def render_attributes(verts: torch.Tensor, faces, intr, size, attr: torch.Tensor
     bg = np.atleast_1d(np.asarray(background, np.float32))
     if bg.ndim != 1 or bg.shape[0] not in (1, C):
         raise ValueError(f"background must be a float or {C} floats")
-    return _RenderAttributes.apply(attr, verts, faces, intr, size, bg, float(z_near), bool(cull_backfaces))
+    image, face, _ = _RenderAttributes.apply(attr, verts, faces, intr, size, bg, float(z_near), bool(cull_backfaces), bool(interior))
+    return image, face
 
 
 # ---- silhouette-edge antialiasing: the render's coverage as a smooth function of the vertices -----------------------------------
@@ -2242,6 +2305,76 @@ class PhotometricTerm(torch.nn.Module):
             n_cut = (sq.detach() > self.trunc * self.trunc).sum()
             rho = torch.clamp(sq, max=self.trunc * self.trunc)
         return {"cost": rho.sum(), "gate": gate, "valid": valid, "value": value, "sq": sq, "n_truncated": n_cut}
+
+    def forward(self, verts: torch.Tensor, colours: torch.Tensor) -> torch.Tensor:
+        return self.evaluate(verts, colours)["cost"]
+
+
+class RenderedPhotometricTerm(torch.nn.Module):
+    """The DENSE photometric term, PhotometricTerm's counterpart at the pixels: the rendered vertex colours against the video.
+
+    images: [F, H, W, C] or [F, H, W], uint8 (raw 0 .. 255) or float32, on the GPU; intr = (fx, fy, cx, cy).  term(verts, colours),
+    verts [F, V, 3] f32 and colours [V, C] or [F, V, C] f32 in the images' units, returns the f64 cost
+      sum over the pixels p of mask of rho(sum_c (R_c(p) - I_c(p))^2),    rho(s) = min(s, trunc^2) (trunc None: rho(s) = s),
+    R = antialias(render_attributes(verts, colours, background, interior=True)) (antialias=False: the render itself) and I the
+    images; mask: bool or uint8 [F, H, W] on the GPU (None: every pixel).  PhotometricTerm samples the video at the 6,890
+    vertices; this term compares every pixel the mesh covers, and the uncovered ones against background.  Differentiable in
+    verts through the interpolation inside the faces (render_attributes' interior) and, with antialias, through coverage
+    at the silhouettes; in colours through both.  One render per evaluation, shared by the two.  No normal equations are built
+    for it.  evaluate(verts, colours) returns the cost with its parts."""
+
+    def __init__(self, images: torch.Tensor, intr, faces, trunc: float | None = None, background=0.0, mask: torch.Tensor | None = None,
+                 antialias: bool = True, z_near: float = 0.1, cull_backfaces: bool = False):
+        super().__init__()
+        img, _ = _check_images(images)
+        if len(intr) != 4:
+            raise ValueError("intr is (fx, fy, cx, cy)")
+        if not z_near > 0.0:
+            raise ValueError("z_near must be positive")
+        if trunc is not None and not trunc > 0.0:
+            raise ValueError("trunc must be positive")
+        C = int(img.shape[3])
+        bg = np.atleast_1d(np.asarray(background, np.float32))
+        if bg.ndim != 1 or bg.shape[0] not in (1, C):
+            raise ValueError(f"background must be a float or {C} floats")
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or mask.device != img.device:
+                raise TypeError("mask must be a bool or uint8 tensor [F, H, W] on the GPU of the images")
+            if tuple(mask.shape) != tuple(img.shape[:3]):
+                raise ValueError(f"mask must be {tuple(img.shape[:3])}, got {tuple(mask.shape)}")
+        self.intr = tuple(float(a) for a in intr)
+        self.size, self.z_near, self.cull_backfaces = (int(img.shape[1]), int(img.shape[2])), float(z_near), bool(cull_backfaces)
+        self.trunc = None if trunc is None else float(trunc)
+        self.background, self.antialias = bg, bool(antialias)
+        self.faces = _host_faces(faces).copy()
+        self.register_buffer("images", img)
+        self.register_buffer("mask", None if mask is None else (mask != 0).contiguous())
+
+    def evaluate(self, verts: torch.Tensor, colours: torch.Tensor) -> dict:
+        """term(verts, colours) with what it was built from: cost (f64, with the gradient), image f32 [F, H, W, C] (what was
+        compared with the video: antialiased or not), the render (depth, face), sq f64 [F, H, W] (the squared colour distance of a
+        pixel of the mask, else 0) and n_truncated"""
+        _check_verts(verts)
+        F, V = verts.shape[0], verts.shape[1]
+        _check_per_vertex(colours, "colours", F, V, verts.device)
+        if self.images.device != verts.device or self.images.shape[0] != F:
+            raise ValueError(f"the images have {self.images.shape[0]} frames on {self.images.device}, verts has {F} on {verts.device}")
+        if colours.shape[-1] != self.images.shape[3]:
+            raise ValueError(f"colours has {colours.shape[-1]} channels, the images {self.images.shape[3]}")
+        image, face, depth = _RenderAttributes.apply(colours, verts, self.faces, self.intr, self.size, self.background, self.z_near,
+                                                     self.cull_backfaces, True)
+        if self.antialias:
+            image = antialias(image, verts, self.faces, self.intr, render=(depth, face), z_near=self.z_near,
+                              cull_backfaces=self.cull_backfaces)
+        sq = (image.double() - self.images.double()).square().sum(dim=-1)
+        if self.mask is not None:
+            sq = torch.where(self.mask, sq, torch.zeros((), dtype=torch.float64, device=verts.device))
+        n_cut = torch.zeros((), dtype=torch.long, device=verts.device)
+        rho = sq
+        if self.trunc is not None:
+            n_cut = (sq.detach() > self.trunc * self.trunc).sum()
+            rho = torch.clamp(sq, max=self.trunc * self.trunc)
+        return {"cost": rho.sum(), "image": image, "depth": depth, "face": face, "sq": sq, "n_truncated": n_cut}
 
     def forward(self, verts: torch.Tensor, colours: torch.Tensor) -> torch.Tensor:
         return self.evaluate(verts, colours)["cost"]

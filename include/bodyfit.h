@@ -1018,6 +1018,79 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
                                      const int32_t* d_pixel /* may be NULL */, const int32_t* d_offset /* may be NULL */,
                                      long long n_rows, int32_t* d_index, float* d_z /* may be NULL */,
                                      float* d_bary /* may be NULL */, float* d_dir /* may be NULL */, void* stream);
+/* INTERPOLATION ROWS: the gradient of vertex attributes interpolated over a face, and of the ray-plane depth, in the face's three
+ * corners, at the correspondence a render already holds (k_rs_interp_rows, k_raster.hip).  What bodyfit_raster_shade_device lacks:
+ * how a pixel's colour changes when its face moves under the fixed pixel ray.  Rows, d_face_image, d_pixel, d_offset and n_rows are
+ * exactly those of bodyfit_raster_depth_rows_device.  d_attr f32 rows of n_channels floats per vertex, attr_frame_stride floats
+ * between frames (0: shared by the frames, else >= n_channels n_verts), as in bodyfit_raster_shade_device; d_grad_image f32
+ * [n_frames][H][W][n_channels] = G = dL/dimage and d_grad_z f32 [n_frames][H][W] = g_z = dL/dz or NULL, both DENSE images: a row
+ * reads them at its own (frame, pixel), so nothing is gathered before the call.  n_channels in 0 .. 4; 0 (d_attr and d_grad_image
+ * may be NULL) is the depth-only case, which needs d_grad_z.  Outputs, packed per row: d_index int32 [N] the face or -1, d_bary f32
+ * [N][3], d_dir f32 [N][3], d_value f32 [N][n_channels]; any of the last three may be NULL.  Every row is written, whatever the
+ * outputs held.
+ * DEFINITION.  With d, n, D, z, x, beta and m of bodyfit_raster_depth_rows_device and A_a the attribute row of corner a, the
+ * interpolated value is I_ch = sum_a beta_a A_a,ch (d_value).  At the fixed face and the fixed ray let
+ *   g_a = n x (v_c - v_b) / (n . n)   (b, c the corners after a): the in-plane gradient of beta_a, g_a . n = 0, sum_a g_a = 0,
+ *   h_a = g_a - (g_a . d / D) n = g_a - (g_a . d) m:   h_a . d = 0, sum_a h_a = 0, |h_a|^2 = |g_a|^2 + (g_a . d)^2 |m|^2.
+ * Moving corner c by delta moves the plane's point on the ray by (beta_c m . delta) d (the depth rows' dz/dv_c = beta_c m^T), and a
+ * point that stays in the plane keeps sum_b beta_b (v_b - x) = 0: differentiating, with g_a the derivative of beta_a in the point,
+ * gives dbeta_a/dv_c = -beta_c h_a^T.  So for upstream gradients G_ch and g_z
+ *   dL/dv_c = beta_c dir,   dir = g_z m - sum_a s_a h_a,   s_a = sum_ch G_ch A_a,ch:
+ * ONE row of bodyfit_surface_rows_vjp_device per pixel whatever n_channels (index = the face, bary = beta, coef = 1, direction =
+ * dir).  dir . d = g_z; three equal s_a (a face of one colour) give dir = g_z m exactly.
+ * VOID rows are the depth rows': index -1, beta = 0, dir = 0, value = 0.  Attributes and upstream gradients are plain IEEE: a NaN
+ * or an infinity there gives a non-finite dir (and value) and does NOT void the row; those of a void row are never read.
+ * CONTRACT, with u = 2^-24, k_i = 2, P, L, Q, rho, c and kappa_b of the depth rows, and per non-void row
+ *   sigma_a = sum_ch |G_ch A_a,ch|,   T = |g_z| |m| + sum_a |s_a| |h_a|,   T_1 = |g_z| |m| + sum_a sigma_a |h_a|   (T <= T_1, equal
+ *       for n_channels <= 1 and wherever the channels of a corner do not cancel in s_a),
+ *   kappa_d = 2^-19 rho Q / c,   V_ch = sum_a |beta_a A_a,ch|,   A_ch = sum_a |A_a,ch|:
+ *   |dir^_c - dir_c| <= k_i u T + kappa_d u T_1,     |value^_ch - I_ch| <= k_i u V_ch + kappa_b u max(1, |beta|) A_ch,
+ * and index and beta are the depth rows', bit for bit (the same operations in the same order).  The bound is relative to T, not
+ * to |dir|: the three h_a sum to 0, so |dir| can be far below T and no evaluation from rounded corners keeps a bound relative to
+ * it.  The first term is the store's rounding, the second the f64 evaluation under the face's conditioning: for the 2 cm face of
+ * a body at 3 m of the depth rows' example kappa_d = 2^-11 and the bound is 2 u T.
+ * Evaluation order, chosen so that equal s_a cancel EXACTLY: s_a = ((G_0 A_a0 + G_1 A_a1) + G_2 A_a2) + G_3 A_a3 (a product of
+ * two f32 is exact in f64), the DIFFERENCES p = s_1 - s_0 and q = s_2 - s_0 against s_0, E = q e1 - p e2 with the depth rows' e1 =
+ * v1 - v0 and e2 = v2 - v0 (E = sum_a s_a (v_c - v_b)), w = (n x E) (1 / (n . n)) = sum_a s_a g_a, k = (w_x d_x + w_y d_y) + w_z,
+ * a = w - k m = sum_a s_a h_a, dir = g_z m - a; value_ch = (beta_0 A_0ch + beta_1 A_1ch) + beta_2 A_2ch from the unrounded beta.
+ * Derivation (eps = 2^-53 = 2^-29 u; f64, unfused; S = L^2 / |n| <= 2 Q and the depth rows' |dn| <= 14 eps S |n|, 1 / (n . n) to
+ * (28 S + 5) eps, m_c to 58 eps S / c |m|).  s_a: at most three sums, 3 eps sigma_a.  p, q: one rounding more, |p| + |q| <= 2 Sigma
+ * with Sigma = sigma_0 + sigma_1 + sigma_2.  A component of E, two products of factors off by eps L and their difference:
+ * L (dp + dq + 5 eps (|p| + |q|)) <= 16 eps L Sigma, |dE| <= 28 eps L Sigma.  Every edge has |n| <= |v_c - v_b| sqrt 3 L (the area
+ * is an edge times a height, and a height is below another edge), so L / |n| <= sqrt 3 S |g_a| for EVERY a and L Sigma / |n| <=
+ * sqrt 3 S T_g with T_g = sum_a sigma_a |g_a| <= T_1: the price of the differences (a term in sigma_0 |e1|, which the face's own
+ * T_g need not hold) is one factor S, which kappa_d carries anyway.  w, |w| = |E| / |n| <= T_g: the cross product and the
+ * product with the reciprocal 12 eps, dn 14 eps S, the reciprocal 28 eps S, dE 49 eps S: |dw| <= eps (91 S + 12) T_g.  k: |dk| <=
+ * (|dw| + 8 eps |w|) |d|, and |m| |d| = 1 / c.  k m_c: |k| |m| <= sum_a |s_a| |h_a| (since |g_a . d| |m| <= |h_a|), so dk |m| + |k|
+ * dm_c + eps |k m_c| <= eps ((91 S + 20) / c T_g + (58 S / c + 1) T_1).  a_c = w_c - k m_c rounds once more, 2 eps T_1.  Together
+ *   |da_c| <= eps T_1 (240 S + 35) / c <= 345 eps S T_1 / c <= 690 eps Q T_1 / c = 2^-19.6 Q / c u T_1;
+ * g_z m_c is off by |g_z| |m| 116 eps Q / c, inside the same kappa_d (rho >= 1 is kept so that one number serves both parts; it
+ * multiplies nothing in a).  The last difference and the store: eps and u of |dir^_c| <= T (1 + ...), stated as k_i = 2.  value:
+ * beta^_a before its store is within kappa_b u max(1, |beta|) of beta_a (the depth rows' derivation), three products and two
+ * sums 3 eps V_ch, the store u: k_i = 2.  A row voided although n and D are not 0 has kappa >= 2^24, as a depth row.
+ * AGAINST THE SHADE.  Where d_face_image and the shade's d_bary are this handle's render of the same vertices and intrinsics and
+ * the shade does not void the pixel, the shade's image is sum_a w_a(lambda^) A_a within its k_s u T_ch, w_a(lambda) = (lambda_a /
+ * Z_a) / sum_b (lambda_b / Z_b).  For the EXACT screen-space lambda of the pixel in the face, w_a(lambda) = beta_a (both are the
+ * barycentrics of the ray's point in the plane, inside the face or not), and item (e) of the render's contract keeps lambda^
+ * within tau_t of lambda: each lambda_a / Z_a moves by tau_t / Z_a, their sum by at most 3 tau_t R_t of itself, so |w_a(lambda^) -
+ * beta_a| <= 5 tau_t R_t (for tau_t R_t <= 1/16: 4 to first order).  So at every such pixel
+ *   |value_row_ch - image_shade_ch| <= k_i u V_ch + kappa_b u max(1, |beta|) A_ch + k_s u T_ch + 5 tau_t R_t A_ch:
+ * the two contracts and the render's summed.
+ * One thread per row: a gather of the face's 36 bytes of corners and 12 n_channels bytes of attributes, the upstream gradients
+ * streamed at the row's pixel; plain stores, no atomics, no workspace: bit-identical from run to run, and a frame's rows depend on
+ * that frame only.  Asynchronous on `stream`, no host synchronisation.  n_frames == 0 or N == 0: a successful no-op.
+ * BODYFIT_ERR_INVALID (nothing is launched): every case of bodyfit_raster_depth_rows_device (NULL handle, negative n_frames or
+ * n_rows, fx or fy <= 0 or a non-finite intrinsic, d_offset without d_pixel, without d_pixel an n_rows other than n_frames H W, a
+ * uniform d_pixel whose n_rows n_frames does not divide, 2^31 - 4096 rows or more, and with rows to write: NULL d_face_image /
+ * d_index, NULL d_verts (n_faces > 0), a stride below 3 n_verts), n_channels outside 0 .. 4, and with rows to write: NULL d_attr
+ * / d_grad_image with n_channels > 0, a non-zero attribute stride below n_channels n_verts, n_channels == 0 without d_grad_z.     */
+int bodyfit_raster_interp_rows_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                      double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                      const int32_t* d_pixel /* may be NULL */, const int32_t* d_offset /* may be NULL */,
+                                      long long n_rows, const float* d_attr, long long attr_frame_stride, int n_channels,
+                                      const float* d_grad_image, const float* d_grad_z /* may be NULL */, int32_t* d_index,
+                                      float* d_bary /* may be NULL */, float* d_dir /* may be NULL */,
+                                      float* d_value /* may be NULL */, void* stream);
 /* DISTANCE TRANSFORM with the nearest seed (a feature transform) of n_frames masks of the handle's size (k_edt.hip): what a
  * silhouette term needs of a person mask and of a rendered face-id image.  seed_kind 0: d_seed is u8 [n_frames][H][W] and a
  * pixel is a SEED iff its byte is != 0 (a bool image qualifies); seed_kind 1: d_seed is int32 [n_frames][H][W] and a pixel is
