@@ -301,6 +301,18 @@ def load_library():
                                                     C.c_double, C.c_double, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_interp_rows_indexed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                                              C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int,
+                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_texture_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int,
+                                                  C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_texture_grad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
     _lib = lib
     return lib
 
@@ -1071,6 +1083,57 @@ class Raster:
                                                                 d_attr_ptr, int(attr_frame_stride), int(n_channels),
                                                                 d_grad_image_ptr, d_grad_z_ptr, d_index_ptr, d_bary_ptr,
                                                                 d_dir_ptr, d_value_ptr, stream))
+
+    def interp_rows_indexed_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, intr, d_face_image_ptr: int,
+                                   d_pixel_ptr: int | None, d_offset_ptr: int | None, n_rows: int, d_attr_ptr: int | None,
+                                   attr_frame_stride: int, n_channels: int, d_attr_faces_ptr: int | None, n_attr_rows: int,
+                                   d_grad_image_ptr: int | None, d_grad_z_ptr: int | None, d_index_ptr: int,
+                                   d_bary_ptr: int | None = None, d_dir_ptr: int | None = None, d_value_ptr: int | None = None,
+                                   stream: int | None = None):
+        """bodyfit_raster_interp_rows_indexed_device: interp_rows_device with the attribute rows of a face taken from
+        attr_faces int32 [n_faces, 3] (device; entries in [0, n_attr_rows), anything else voids the face's rows) instead of the
+        corners' vertex ids: per-corner attributes such as the rows of a uv atlas.  Asynchronous on `stream`."""
+        _check(load_library().bodyfit_raster_interp_rows_indexed_device(
+            self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames), float(intr[0]), float(intr[1]), float(intr[2]),
+            float(intr[3]), d_face_image_ptr, d_pixel_ptr, d_offset_ptr, int(n_rows), d_attr_ptr, int(attr_frame_stride),
+            int(n_channels), d_attr_faces_ptr, int(n_attr_rows), d_grad_image_ptr, d_grad_z_ptr, d_index_ptr, d_bary_ptr, d_dir_ptr,
+            d_value_ptr, stream))
+
+    def texture_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                       d_uv_ptr: int | None, n_uv: int, d_uv_faces_ptr: int | None, d_tex_ptr: int | None, tex_kind: int,
+                       n_channels: int, tex_height: int, tex_width: int, tex_frame_stride: int, n_frames: int, background,
+                       d_image_ptr: int, d_weight_ptr: int | None = None, d_uv_out_ptr: int | None = None,
+                       stream: int | None = None):
+        """bodyfit_raster_texture_device: the texture [Ht, Wt, n_channels] (tex_kind 0: u8, raw 0 .. 255; 1: f32;
+        tex_frame_stride elements between the frames' textures, 0: shared) looked up bilinearly, clamp-to-edge, at the uv of
+        every pixel of a render (face [F, H, W] int32, bary [F, H, W, 3] f32): uv f32 [n_uv, 2] and uv_faces int32 [n_faces, 3]
+        on the device, interpolated with the shade's perspective-correct weights.  image [F, H, W, n_channels] f32 and, unless
+        None, weight [F, H, W, 3] f32 (the shade's) and uv_out [F, H, W, 2] f32.  background: a float or up to four floats.
+        Asynchronous on `stream`, no host synchronisation."""
+        bg = np.zeros(4, np.float32)
+        b = np.atleast_1d(np.asarray(background, np.float32))
+        if b.ndim != 1 or b.shape[0] > 4:
+            raise ValueError("background is a float or up to four floats")
+        bg[:4 if b.shape[0] == 1 else b.shape[0]] = b          # (one float: every channel)
+        _check(load_library().bodyfit_raster_texture_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_uv_ptr, int(n_uv), d_uv_faces_ptr, d_tex_ptr,
+            int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames),
+            bg.ctypes.data_as(C.POINTER(C.c_float)), d_image_ptr, d_weight_ptr, d_uv_out_ptr, stream))
+
+    def texture_grad_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                            d_uv_ptr: int | None, n_uv: int, d_uv_faces_ptr: int | None, d_tex_ptr: int | None, tex_kind: int,
+                            n_channels: int, tex_height: int, tex_width: int, tex_frame_stride: int, n_frames: int,
+                            d_grad_image_ptr: int, d_grad_uv_ptr: int | None, d_grad_tex_ptr: int | None,
+                            d_workspace_ptr: int | None, stream: int | None = None):
+        """bodyfit_raster_texture_grad_device: for grad_image [F, H, W, n_channels] f32 the gradient of texture_device's image
+        in the pixels' uv, grad_uv [F, H, W, 2] f32 (or None), and in the texels, grad_tex f32 [Ht, Wt, n_channels] (a shared
+        texture: summed over the frames) or [F, Ht, Wt, n_channels] (or None; tex may then be None), summed exactly in the int64
+        workspace of grad_tex's shape: no float atomics, bit-identical whatever the order.  Asynchronous on `stream`, no host
+        synchronisation."""
+        _check(load_library().bodyfit_raster_texture_grad_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_uv_ptr, int(n_uv), d_uv_faces_ptr, d_tex_ptr,
+            int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames), d_grad_image_ptr,
+            d_grad_uv_ptr, d_grad_tex_ptr, d_workspace_ptr, stream))
 
     def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_frame_stride: int, n_frames: int, invert: bool,
                         d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):

@@ -16,13 +16,15 @@
 //   k_rs_depth_rows one thread per depth row (a pixel of a frame): the ray through the pixel against the plane of the face the
 //                face-id image holds there: z, the object-space barycentrics and the direction m with dz/dcorner_a = beta_a m
 //                (bodyfit_raster_depth_rows_device), f64 throughout, plain stores
-//   k_rs_interp_rows<C> one thread per interpolation row: the depth row's face, ray and beta, and the one direction dir with
-//                dL/dcorner_c = beta_c dir for upstream gradients in the interpolated attributes and in z
-//                (bodyfit_raster_interp_rows_device), f64 throughout, plain stores
+//   k_rs_interp_rows<C, kIndexed> one thread per interpolation row: the depth row's face, ray and beta, and the one direction dir
+//                with dL/dcorner_c = beta_c dir for upstream gradients in the interpolated attributes and in z
+//                (bodyfit_raster_interp_rows_device; kIndexed: the attribute rows of a face from a table of their own, a uv atlas:
+//                bodyfit_raster_interp_rows_indexed_device), f64 throughout, plain stores
 //   k_rs_shade<C>  one thread per pixel of a render: per-vertex attributes interpolated with the perspective-correct weights
 //                (lambda_a / Z_a) / sum, the background where the pixel is void (bodyfit_raster_shade_device)
 //   k_rs_sample<C, T>  one thread per (frame, point): the point's projection, the bilinear value of a u8 or f32 image there and
-//                the derivative of the cell's patch (bodyfit_raster_sample_device)
+//                the derivative of the cell's patch (bodyfit_raster_sample_device; the patch is bilinear_inl.h's, shared with
+//                k_texture.hip)
 //   k_rs_edges   one thread per pixel: its right and lower neighbour pairs; where the two face ids differ, the bounded walk from
 //                the nearer pixel's face to the silhouette edge that crosses the segment between the two centres, and the blend
 //                weight (bodyfit_raster_edges_device)
@@ -48,9 +50,11 @@
 #include <vector>
 
 #include "../../include/bodyfit.h"
+#include "bilinear_inl.h"
 #include "bodyfit_device.h"
 #include "edt.h"
 #include "host_state.h"
+#include "raster_view.h"
 #include "solver_view.h"
 
 #pragma clang fp contract(off)
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(256) void k_rs_depth_rows(const float* __restrict__
 //   dir = g_z m - a,  value_c = (beta_0 A_0c + beta_1 A_1c) + beta_2 A_2c from the unrounded beta.
 // C = 0: no attributes, dir = g_z m.  The row reads the upstream gradients at its own (frame, pixel): nothing is gathered before
 // the call.  Only the stores round to f32.
-template <int C>
+template <int C, bool kIndexed>
 __global__ __launch_bounds__(256) void k_rs_interp_rows(const float* __restrict__ verts, long long frame_stride,
                                                         const int* __restrict__ faces, int nF, int F, int W, int H, double fx,
                                                         double fy, double cx, double cy, const int* __restrict__ face_img,
@@ -313,7 +317,8 @@ __global__ __launch_bounds__(256) void k_rs_interp_rows(const float* __restrict_
                                                         long long attr_stride, const float* __restrict__ grad_image,
                                                         const float* __restrict__ grad_z, int* __restrict__ index,
                                                         float* __restrict__ bary, float* __restrict__ dir,
-                                                        float* __restrict__ value) {
+                                                        float* __restrict__ value, const int* __restrict__ attr_faces,
+                                                        int n_attr_rows) {
   const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
   if (row >= n_rows) return;
   const long long ppf = (long long)W * H;
@@ -330,12 +335,20 @@ __global__ __launch_bounds__(256) void k_rs_interp_rows(const float* __restrict_
   bool ok = (unsigned)f < (unsigned)nF;     // empty (-1), not a face of this topology, or a pixel outside the image
   double b[3] = {0.0, 0.0, 0.0}, r[3] = {0.0, 0.0, 0.0};
   double val[C > 0 ? C : 1] = {};
+  size_t aid[3] = {0, 0, 0};     // the rows of attr: the corners' vertex ids, or (kIndexed) the face's own three entries
+  if (kIndexed && C > 0 && ok)
+    for (int k = 0; k < 3; ++k) {
+      const int e = attr_faces[3 * f + k];
+      if ((unsigned)e >= (unsigned)n_attr_rows) ok = false;     // an entry out of range voids the rows of that face
+      aid[k] = (size_t)e;
+    }
   if (ok) {
     const float* c = verts + (size_t)frame * (size_t)frame_stride;
     size_t id[3];
     double v[3][3];
     for (int k = 0; k < 3; ++k) {
       id[k] = (size_t)faces[3 * f + k];
+      if (!kIndexed) aid[k] = id[k];
       for (int a = 0; a < 3; ++a) {
         const float X = c[3 * id[k] + a];
         if (!(X - X == 0.0f)) ok = false;   // (a NaN fails every comparison; X - X is NaN for an infinity)
@@ -375,7 +388,7 @@ __global__ __launch_bounds__(256) void k_rs_interp_rows(const float* __restrict_
         for (int k = 0; k < 3; ++k) {
           double acc = 0.0;
           for (int ch = 0; ch < C; ++ch) {
-            const double Ak = (double)A[C * id[k] + ch];
+            const double Ak = (double)A[C * aid[k] + ch];
             const double t = (double)grad_image[C * at + ch] * Ak;
             acc = ch == 0 ? t : acc + t;
             const double bt = b[k] * Ak;
@@ -468,24 +481,8 @@ __global__ __launch_bounds__(256) void k_rs_sample(const float* __restrict__ poi
     const double u = fx * ((double)X / (double)Z) + cx, v = fy * ((double)Y / (double)Z) + cy;
     ok = u >= 0.0 && u <= (double)(W - 1) && v >= 0.0 && v <= (double)(H - 1);
     if (ok) {
-      const int j0 = min((int)floor(u), max(W - 2, 0)), j1 = min(j0 + 1, W - 1);
-      const int i0 = min((int)floor(v), max(H - 2, 0)), i1 = min(i0 + 1, H - 1);
-      const double a = u - (double)j0, b = v - (double)i0;
-      const T* img = image + frame * (size_t)image_stride;
-      const T* r0 = img + ((size_t)i0 * W) * C;
-      const T* r1 = img + ((size_t)i1 * W) * C;
-      T t00[C], t01[C], t10[C], t11[C];
-      for (int c = 0; c < C; ++c) {
-        t00[c] = r0[(size_t)j0 * C + c]; t01[c] = r0[(size_t)j1 * C + c];
-        t10[c] = r1[(size_t)j0 * C + c]; t11[c] = r1[(size_t)j1 * C + c];
-      }
-      const double na = 1.0 - a, nb = 1.0 - b;
-      for (int c = 0; c < C; ++c) {
-        const double I00 = (double)t00[c], I01 = (double)t01[c], I10 = (double)t10[c], I11 = (double)t11[c];
-        val[c] = ((na * nb) * I00 + (a * nb) * I01) + ((na * b) * I10 + (a * b) * I11);
-        gu[c] = nb * (I01 - I00) + b * (I11 - I10);
-        gv[c] = na * (I10 - I00) + a * (I11 - I01);
-      }
+      const bodyfit::BilinearCell cell = bodyfit::bilinear_cell(u, v, W, H);
+      bodyfit::bilinear_patch<C, T>(image + frame * (size_t)image_stride, W, cell, val, gu, gv);
     }
   }
   valid[p] = ok ? 1 : 0;
@@ -774,6 +771,12 @@ struct bodyfit_raster {
   }
 };
 
+namespace bodyfit {
+RasterView raster_view(const bodyfit_raster* r) {      // (d_totals[2]: the render uses [0] and [1] only)
+  return RasterView{r->device, r->nV, r->nF, r->W, r->H, r->d_faces, r->d_totals + 2};
+}
+}  // namespace bodyfit
+
 namespace {
 // (face, edge) -> the lowest-id OTHER face that holds both vertex ids of the edge (corner e, corner (e + 1) % 3), -1 if none or if
 // the two ids are equal: the (key, face) pairs sorted, each group scanned once
@@ -828,6 +831,65 @@ void rs_launch_sample(int C, dim3 grid, hipStream_t st, const float* d_points, l
     case 3: launch(k_rs_sample<3, T>); break;
     default: launch(k_rs_sample<4, T>); break;
   }
+}
+}  // namespace
+
+namespace {
+// the two interpolation-row entries: one validation, one launch (indexed: attr rows by d_attr_faces, else by the corners' ids)
+int rs_interp_rows(const char* fn, bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames, double fx,
+                   double fy, double cx, double cy, const int32_t* d_face_image, const int32_t* d_pixel, const int32_t* d_offset,
+                   long long n_rows, const float* d_attr, long long attr_frame_stride, int n_channels, bool indexed,
+                   const int32_t* d_attr_faces, int n_attr_rows, const float* d_grad_image, const float* d_grad_z, int32_t* d_index,
+                   float* d_bary, float* d_dir, float* d_value, void* stream) {
+  if (!r) return rs_invalid(fn, "handle is NULL");
+  if (n_frames < 0 || n_rows < 0) return rs_invalid(fn, "negative n_frames or n_rows");
+  if (!(fx > 0.0 && fy > 0.0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)))
+    return rs_invalid(fn, "fx and fy must be positive, and the intrinsics finite");
+  if (n_channels < 0 || n_channels > 4) return rs_invalid(fn, "n_channels outside 0 .. 4");
+  if (indexed && n_attr_rows < 0) return rs_invalid(fn, "negative n_attr_rows");
+  if (d_offset && !d_pixel) return rs_invalid(fn, "d_offset without d_pixel");
+  const long long ppf = (long long)r->W * r->H;
+  if (!d_pixel && n_rows != ppf * n_frames) return rs_invalid(fn, "without d_pixel n_rows must be n_frames H W");
+  if (n_rows >= (1ll << 31) - 4096) return rs_invalid(fn, "2^31 rows or more in one call");
+  if (n_rows > 0 && n_frames == 0) return rs_invalid(fn, "rows without frames");
+  if (d_pixel && !d_offset && n_frames > 0 && n_rows % n_frames != 0)
+    return rs_invalid(fn, "a uniform row set needs n_rows divisible by n_frames");
+  if (n_frames == 0 || n_rows == 0) return BODYFIT_OK;
+  if (!d_face_image || !d_index) return rs_invalid(fn, "d_face_image or d_index is NULL");
+  if (r->nF > 0 && !d_verts) return rs_invalid(fn, "d_verts is NULL");
+  if (verts_frame_stride < 3ll * r->nV) return rs_invalid(fn, "verts_frame_stride below 3 n_verts");
+  if (n_channels > 0 && (!d_attr || !d_grad_image)) return rs_invalid(fn, "d_attr or d_grad_image is NULL with n_channels > 0");
+  if (n_channels > 0 && attr_frame_stride != 0 && attr_frame_stride < (long long)n_channels * n_attr_rows)
+    return rs_invalid(fn, indexed ? "a non-zero attr_frame_stride below n_channels n_attr_rows"
+                                  : "a non-zero attr_frame_stride below n_channels n_verts");
+  if (indexed && n_channels > 0 && r->nF > 0 && !d_attr_faces) return rs_invalid(fn, "d_attr_faces is NULL");
+  if (n_channels == 0 && !d_grad_z) return rs_invalid(fn, "n_channels == 0 needs d_grad_z");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((n_rows + 255) / 256));
+  auto launch = [&](auto kernel) {
+    BODYFIT_LAUNCH(kernel, grid, dim3(256), 0, st, d_verts, verts_frame_stride, r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy,
+                   cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames, n_rows, d_attr, attr_frame_stride, d_grad_image,
+                   d_grad_z, d_index, d_bary, d_dir, d_value, d_attr_faces, n_attr_rows);
+  };
+  // (the un-indexed entry launches what it always has; C = 0 reads no attributes: one instantiation serves both)
+  if (indexed && n_channels > 0)
+    switch (n_channels) {
+      case 1: launch(k_rs_interp_rows<1, true>); break;
+      case 2: launch(k_rs_interp_rows<2, true>); break;
+      case 3: launch(k_rs_interp_rows<3, true>); break;
+      default: launch(k_rs_interp_rows<4, true>); break;
+    }
+  else
+    switch (n_channels) {
+      case 0: launch(k_rs_interp_rows<0, false>); break;
+      case 1: launch(k_rs_interp_rows<1, false>); break;
+      case 2: launch(k_rs_interp_rows<2, false>); break;
+      case 3: launch(k_rs_interp_rows<3, false>); break;
+      default: launch(k_rs_interp_rows<4, false>); break;
+    }
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
 }
 }  // namespace
 
@@ -977,44 +1039,21 @@ int bodyfit_raster_interp_rows_device(bodyfit_raster* r, const float* d_verts, l
                                       long long attr_frame_stride, int n_channels, const float* d_grad_image,
                                       const float* d_grad_z, int32_t* d_index, float* d_bary, float* d_dir, float* d_value,
                                       void* stream) {
-  const char* fn = "bodyfit_raster_interp_rows_device";
-  if (!r) return rs_invalid(fn, "handle is NULL");
-  if (n_frames < 0 || n_rows < 0) return rs_invalid(fn, "negative n_frames or n_rows");
-  if (!(fx > 0.0 && fy > 0.0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy)))
-    return rs_invalid(fn, "fx and fy must be positive, and the intrinsics finite");
-  if (n_channels < 0 || n_channels > 4) return rs_invalid(fn, "n_channels outside 0 .. 4");
-  if (d_offset && !d_pixel) return rs_invalid(fn, "d_offset without d_pixel");
-  const long long ppf = (long long)r->W * r->H;
-  if (!d_pixel && n_rows != ppf * n_frames) return rs_invalid(fn, "without d_pixel n_rows must be n_frames H W");
-  if (n_rows >= (1ll << 31) - 4096) return rs_invalid(fn, "2^31 rows or more in one call");
-  if (n_rows > 0 && n_frames == 0) return rs_invalid(fn, "rows without frames");
-  if (d_pixel && !d_offset && n_frames > 0 && n_rows % n_frames != 0)
-    return rs_invalid(fn, "a uniform row set needs n_rows divisible by n_frames");
-  if (n_frames == 0 || n_rows == 0) return BODYFIT_OK;
-  if (!d_face_image || !d_index) return rs_invalid(fn, "d_face_image or d_index is NULL");
-  if (r->nF > 0 && !d_verts) return rs_invalid(fn, "d_verts is NULL");
-  if (verts_frame_stride < 3ll * r->nV) return rs_invalid(fn, "verts_frame_stride below 3 n_verts");
-  if (n_channels > 0 && (!d_attr || !d_grad_image)) return rs_invalid(fn, "d_attr or d_grad_image is NULL with n_channels > 0");
-  if (n_channels > 0 && attr_frame_stride != 0 && attr_frame_stride < (long long)n_channels * r->nV)
-    return rs_invalid(fn, "a non-zero attr_frame_stride below n_channels n_verts");
-  if (n_channels == 0 && !d_grad_z) return rs_invalid(fn, "n_channels == 0 needs d_grad_z");
-  HIP_TRY(hipSetDevice(r->device));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((n_rows + 255) / 256));
-  auto launch = [&](auto kernel) {
-    BODYFIT_LAUNCH(kernel, grid, dim3(256), 0, st, d_verts, verts_frame_stride, r->d_faces, r->nF, n_frames, r->W, r->H, fx, fy,
-                   cx, cy, d_face_image, d_pixel, d_offset, n_rows / n_frames, n_rows, d_attr, attr_frame_stride, d_grad_image,
-                   d_grad_z, d_index, d_bary, d_dir, d_value);
-  };
-  switch (n_channels) {
-    case 0: launch(k_rs_interp_rows<0>); break;
-    case 1: launch(k_rs_interp_rows<1>); break;
-    case 2: launch(k_rs_interp_rows<2>); break;
-    case 3: launch(k_rs_interp_rows<3>); break;
-    default: launch(k_rs_interp_rows<4>); break;
-  }
-  HIP_TRY(hipGetLastError());
-  return BODYFIT_OK;
+  return rs_interp_rows("bodyfit_raster_interp_rows_device", r, d_verts, verts_frame_stride, n_frames, fx, fy, cx, cy, d_face_image,
+                        d_pixel, d_offset, n_rows, d_attr, attr_frame_stride, n_channels, false, nullptr, r ? r->nV : 0,
+                        d_grad_image, d_grad_z, d_index, d_bary, d_dir, d_value, stream);
+}
+
+int bodyfit_raster_interp_rows_indexed_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                              double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                              const int32_t* d_pixel, const int32_t* d_offset, long long n_rows,
+                                              const float* d_attr, long long attr_frame_stride, int n_channels,
+                                              const int32_t* d_attr_faces, int n_attr_rows, const float* d_grad_image,
+                                              const float* d_grad_z, int32_t* d_index, float* d_bary, float* d_dir,
+                                              float* d_value, void* stream) {
+  return rs_interp_rows("bodyfit_raster_interp_rows_indexed_device", r, d_verts, verts_frame_stride, n_frames, fx, fy, cx, cy,
+                        d_face_image, d_pixel, d_offset, n_rows, d_attr, attr_frame_stride, n_channels, true, d_attr_faces,
+                        n_attr_rows, d_grad_image, d_grad_z, d_index, d_bary, d_dir, d_value, stream);
 }
 
 int bodyfit_raster_shade_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,

@@ -164,6 +164,56 @@ def make_faces(model: "SynthModel", n_faces: int = N_FACES, seed: int = 0) -> np
     return np.ascontiguousarray(f, dtype=np.int32)
 
 
+def make_uv_atlas(faces, kind: str = "charts", verts=None, inset: float = 0.13):
+    """A synthetic uv atlas for the triangles faces [n_faces, 3] (SMPL's own is licensed data): (uv [T, 2] f32, uv_faces
+    [n_faces, 3] int32), the rows of uv per face CORNER, all of it inside [inset, 1 - inset]^2 so that a texture of 1 / (2 inset)
+    texels or more each way is never addressed in its clamped border (0.13, not 1/8: on test scenes with dyadic coordinates a
+    dyadic inset puts whole rows of pixels exactly on texel borders, where the lookup's derivative jumps).
+    "charts": every face gets its own right triangle, drawn 11 % inside its cell of a square grid: T = 3 n_faces, a seam at every
+    edge (the hardest atlas: no two faces share a uv row).
+    "cylinder": ONE unwrapping of the vertices verts [V, 3] about the vertical (y) axis through their centroid, u from the angle
+    and v from the height; the faces that straddle the angle's jump get duplicates of their low-angle vertices one turn further,
+    so T = V + the number of duplicated vertices and the only seam is that jump."""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    nf = len(f)
+    if not 0.0 <= inset < 0.5:
+        raise ValueError("inset must be in [0, 0.5)")
+    if kind == "charts":
+        g = max(1, int(np.ceil(np.sqrt(nf))))
+        t = np.arange(nf)
+        cell = np.stack([t % g, t // g], axis=1).astype(np.float64)                      # (column, row)
+        corner = np.array([[0.11, 0.11], [0.89, 0.11], [0.11, 0.89]])
+        uv = ((cell[:, None, :] + corner[None, :, :]) / g).reshape(-1, 2)
+        uv_faces = np.arange(3 * nf, dtype=np.int32).reshape(nf, 3)
+    elif kind == "cylinder":
+        if verts is None:
+            raise ValueError('the "cylinder" atlas unwraps vertex positions: pass verts [V, 3]')
+        x = np.asarray(verts, np.float64).reshape(-1, 3)
+        c = x.mean(axis=0)
+        turn = (np.arctan2(x[:, 0] - c[0], x[:, 2] - c[2]) + np.pi) / (2.0 * np.pi)      # [0, 1]
+        lo, hi = x[:, 1].min(), x[:, 1].max()
+        height = (x[:, 1] - lo) / max(hi - lo, 1e-12)
+        uv_faces = f.copy()
+        u_rows, v_rows = list(turn), list(height)
+        dup = {}
+        tf = turn[f] if nf else np.zeros((0, 3))
+        for t in np.nonzero(tf.max(axis=1) - tf.min(axis=1) > 0.5)[0]:                    # the face straddles the jump
+            for a in range(3):
+                i = int(f[t, a])
+                if turn[i] < 0.5:
+                    if i not in dup:
+                        dup[i] = len(u_rows)
+                        u_rows.append(turn[i] + 1.0)
+                        v_rows.append(height[i])
+                    uv_faces[t, a] = dup[i]
+        uv = np.stack([np.asarray(u_rows) / max(max(u_rows, default=1.0), 1.0), np.asarray(v_rows)], axis=1)
+        uv_faces = uv_faces.astype(np.int32)
+    else:
+        raise ValueError(f'kind must be "charts" or "cylinder", got {kind!r}')
+    uv = inset + (1.0 - 2.0 * inset) * uv
+    return np.ascontiguousarray(uv, dtype=np.float32), np.ascontiguousarray(uv_faces, dtype=np.int32)
+
+
 def _seg_dist(p, a, b):
     ab = b - a
     t = np.clip(((p - a) @ ab) / max(ab @ ab, 1e-12), 0.0, 1.0)

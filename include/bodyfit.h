@@ -1091,6 +1091,26 @@ int bodyfit_raster_interp_rows_device(bodyfit_raster* r, const float* d_verts, l
                                       const float* d_grad_image, const float* d_grad_z /* may be NULL */, int32_t* d_index,
                                       float* d_bary /* may be NULL */, float* d_dir /* may be NULL */,
                                       float* d_value /* may be NULL */, void* stream);
+/* INTERPOLATION ROWS WITH PER-CORNER ATTRIBUTES (k_rs_interp_rows<C, true>, the same kernel template with one more compile-time
+ * switch): bodyfit_raster_interp_rows_device with the attribute rows of a face taken from a table of their own,
+ *   A_a = attr[attr_faces[t][a]]   instead of   attr[faces[t][a]],
+ * d_attr_faces int32 [n_faces][3] on the DEVICE and n_attr_rows the number of rows of d_attr (per frame); a non-zero
+ * attr_frame_stride is >= n_channels n_attr_rows.  A uv atlas with seams is such a table: a vertex has several uv rows, and
+ * n_attr_rows and n_verts are unrelated.  An entry of d_attr_faces outside [0, n_attr_rows) VOIDS the rows of that face (validated
+ * on the device, as face ids are).  Everything else is bodyfit_raster_interp_rows_device's: the definition, the evaluation order,
+ * the contract, the outputs and the error cases (plus: negative n_attr_rows, NULL d_attr_faces with n_channels > 0 and n_faces > 0);
+ * with d_attr_faces = the topology's faces and n_attr_rows = n_verts the two entries return the same bits.  n_channels == 0 reads
+ * no attributes and launches the un-indexed kernel.
+ * With attr = the uv table, n_channels = 2 and d_grad_image = d_grad_uv of bodyfit_raster_texture_grad_device the rows are
+ * dL/dverts of a textured image through the interpolation inside the faces.                                                       */
+int bodyfit_raster_interp_rows_indexed_device(bodyfit_raster* r, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                              double fx, double fy, double cx, double cy, const int32_t* d_face_image,
+                                              const int32_t* d_pixel /* may be NULL */, const int32_t* d_offset /* may be NULL */,
+                                              long long n_rows, const float* d_attr, long long attr_frame_stride, int n_channels,
+                                              const int32_t* d_attr_faces, int n_attr_rows, const float* d_grad_image,
+                                              const float* d_grad_z /* may be NULL */, int32_t* d_index,
+                                              float* d_bary /* may be NULL */, float* d_dir /* may be NULL */,
+                                              float* d_value /* may be NULL */, void* stream);
 /* DISTANCE TRANSFORM with the nearest seed (a feature transform) of n_frames masks of the handle's size (k_edt.hip): what a
  * silhouette term needs of a person mask and of a rendered face-id image.  seed_kind 0: d_seed is u8 [n_frames][H][W] and a
  * pixel is a SEED iff its byte is != 0 (a bool image qualifies); seed_kind 1: d_seed is int32 [n_frames][H][W] and a pixel is
@@ -1207,6 +1227,114 @@ int bodyfit_raster_sample_device(bodyfit_raster* r, const float* d_points, long 
                                  int image_kind, int n_channels, long long image_frame_stride,
                                  const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
                                  float* d_grad /* may be NULL */, void* stream);
+/* UV TEXTURES OVER A RENDER (k_tx_forward, k_texture.hip): the texture lookup of Laine et al. (2020) without its mipmaps.
+ * ATLAS.  d_uv f32 [n_uv][2] and d_uv_faces int32 [n_faces][3], both on the device: the rows of d_uv per face CORNER.  An atlas has
+ * seams, so a vertex has several uv rows: n_uv and n_verts are unrelated.  TEXTURE.  d_tex: tex_kind 0 = u8 (a texel is its raw
+ * value 0 .. 255, as in bodyfit_raster_sample_device), 1 = f32; [Ht][Wt][n_channels] interleaved, n_channels in 1 .. 4, Ht and Wt in
+ * 1 .. 16384; tex_frame_stride ELEMENTS between the frames' textures: 0 when the frames share one, else >= Ht Wt n_channels.
+ * TEXEL POSITIONS.  Texel (i, j) has its centre at (u, v) = ((j + 1/2) / Wt, (i + 1/2) / Ht); row 0 is at the top, nothing is flipped.
+ * x = u Wt - 1/2, y = v Ht - 1/2.  Addressing is CLAMP-TO-EDGE: x is clamped to [0, Wt - 1] and y to [0, Ht - 1], in f64 and BEFORE
+ * anything is converted to an integer, so a huge or negative uv never becomes an index; then the cell, a and b are the sampler's:
+ * j0 = min(floor(x), max(Wt - 2, 0)), j1 = min(j0 + 1, Wt - 1), a = x - j0, and i0, i1, b alike in y, Ht (one device helper,
+ * bilinear_inl.h, serves both kernels).
+ * d_face, d_bary, d_verts (only the corners' z is read), verts_frame_stride, background and the VOID rule are exactly
+ * bodyfit_raster_shade_device's; in addition a pixel is void when an entry of d_uv_faces of its face is outside [0, n_uv) (validated
+ * on the device) or when its u or v is not finite.  Outputs, dense, every element of every frame written whatever the buffers held:
+ * d_image f32 [n_frames][H][W][n_channels]; unless NULL d_weight f32 [n_frames][H][W][3] and d_uv_out f32 [n_frames][H][W][2].
+ * DEFINITION.  w_a are the shade's weights, formed by the same operations in the same order (d_weight equals the shade's bit for
+ * bit wherever both shade the pixel); with uv_a = uv[uv_faces[t][a]], per component (u, v) = (w_0 uv_0 + w_1 uv_1) + w_2 uv_2;
+ *   image_c = (1 - a)(1 - b) T[i0][j0] + a (1 - b) T[i0][j1] + (1 - a) b T[i1][j0] + a b T[i1][j1]
+ * at the clamped (x, y).  A void pixel gets background[c], weights 0 and uv 0.  Texels are plain IEEE.
+ * CONTRACT, with u = 2^-24, U = max(1, max_a |u_a|, max_a |v_a|) over the face's three uv rows, P_x = max(Wt, Ht), delta = 2^-49 P_x U,
+ * kappa = k_t 2^-50 P_x U with k_t = 16, B the continuous clamp-to-edge bilinear surface through the texels and M the largest
+ * |texel| among the texels of the exact cell and of the returned cell, at every pixel that is not void:
+ *   |image^_c - B_c(x, y)| <= u |B_c| + kappa M,     |uv^ - uv| <= k_s u sum_a w_a |uv_a| per component (k_s = 2, the shade's),
+ * the returned (x^, y^) is within delta of the exact clamped (x, y), and d_weight is the shade's.  A pixel whose exact u or v
+ * overflows nothing here: |uv_a| <= 2^128 and Wt <= 2^14 stay far inside f64.
+ * Derivation (eps = 2^-53; every operation f64 and unfused).  w_a: 5 eps (the shade's derivation).  A product w_a u_a (u_a exact in
+ * f64): 6 eps; the two sums: |du| <= 8 eps sum_a w_a |u_a| <= 8 eps U (1 + 5 eps) (the exact w_a sum to 1).  x^ = u^ Wt - 1/2: the
+ * product and the difference round once each, on magnitudes <= Wt U + 1/2: |dx| <= (8 + 1 + 1.5) eps Wt U <= 11 eps P_x U < delta
+ * = 16 eps P_x U.  The clamp is monotone and does not expand distances: the clamped x^ is within delta of the clamped x; a = x^ - j0
+ * is exact (Sterbenz, or j0 = 0).  B is continuous and piecewise bilinear with slope at most 2 M per texel in each coordinate (0
+ * outside the texel centres' rectangle) and equals the returned cell's patch at (x^, y^): moving by delta each way changes it by at
+ * most 4 M delta = 8 x 2^-50 P_x U M.  The patch in f64 (1 - a, 1 - b, four weight products, four texel products, three sums):
+ * below 8 eps M = 2^-50 M.  Together 9 x 2^-50 P_x U M, stated as k_t = 16; the store rounds once: u |B|.
+ * One thread per pixel, neighbouring lanes on neighbouring columns; the gathers are the shade's plus 24 bytes of uv and the 4
+ * n_channels texels.  Plain stores, no atomics, no workspace: bit-identical from run to run, and a frame's outputs depend on that
+ * frame only.  Asynchronous on `stream`, no host synchronisation.  n_frames == 0: a successful no-op; n_faces == 0: every pixel
+ * background.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames or n_uv, n_channels outside 1 .. 4, tex_kind
+ * outside {0, 1}, Ht or Wt outside 1 .. 16384, a non-zero texture stride below Ht Wt n_channels, and with frames to write: NULL
+ * d_face / d_bary / d_image, NULL d_verts / d_uv_faces / d_tex (n_faces > 0), NULL d_uv (n_faces > 0 and n_uv > 0), a vertex stride
+ * below 3 n_verts, 2^39 pixels or more.
+ * NOT BUILT: mipmaps or any minification filter, the screen-space uv derivatives they need, wrap and mirror addressing.  A body that
+ * is smaller on the screen than its atlas ALIASES (a pixel reads one 2 x 2 cell, whatever area of the atlas it covers), and the
+ * texels no pixel's cell touches receive no gradient.                                                                          */
+int bodyfit_raster_texture_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                  long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                  const void* d_tex, int tex_kind, int n_channels, int tex_height, int tex_width,
+                                  long long tex_frame_stride, int n_frames, const float* background /* host [4]; may be NULL */,
+                                  float* d_image, float* d_weight /* may be NULL */, float* d_uv_out /* may be NULL */,
+                                  void* stream);
+/* THE LOOKUP'S GRADIENTS (k_tx_gmax, k_tx_grad, k_tx_fold, k_texture.hip) for an upstream G = d_grad_image f32 [n_frames][H][W]
+ * [n_channels] = dL/dimage; the other inputs are bodyfit_raster_texture_device's, and the pixel (void rule, weights, uv, clamp,
+ * cell) is evaluated again by the same device function.  Two results, each skipped when its pointer is NULL:
+ * (a) d_grad_uv f32 [n_frames][H][W][2] = (sum_c G_c dimage_c/du, sum_c G_c dimage_c/dv) in uv units: the exact derivative of the
+ *     cell's patch (bodyfit_raster_sample_device's d/du, d/dv) times Wt and Ht; a component is 0 where its clamp is ACTIVE (the
+ *     unclamped x outside [0, Wt - 1], y alike) and both are 0 where the pixel is void.  Order: sum_c as ((G_0 d_0 + G_1 d_1) + G_2 d_2) +
+ *     G_3 d_3, then the product with Wt.  Plain stores, every element written.  Needs d_tex.
+ * (b) d_grad_tex f32 in the texture's layout, [Ht][Wt][n_channels] when the frames share the texture (tex_frame_stride == 0: summed
+ *     over ALL frames) and dense [n_frames][Ht][Wt][n_channels] otherwise, for u8 and f32 textures alike: the exact adjoint of the
+ *     lookup in the texels, g*[i][j][c] = sum over the pixels whose cell holds texel (i, j) of G_c omega_k, omega_k the texel's
+ *     bilinear weight (1 - a)(1 - b), a (1 - b), (1 - a) b or a b at the pixel's returned (x^, y^); where the clamp or a 1-wide texture
+ *     makes two texels of the cell coincide both contributions go to it.  Every element is written.  d_tex is not read for (b).
+ * HOW (b) IS SUMMED: EXACTLY, IN INTEGERS, without float atomics (a many-to-few scatter has no usable order; k_winding.hip's rule).
+ *   1. One pass finds Gmax = max |G| over the WHOLE of d_grad_image (void pixels included) as the u32 bit pattern of |G|: a wave
+ *      reduction and one integer atomicMax per workgroup.  For non-negative floats the patterns order as the values, and every NaN or
+ *      infinity has a pattern >= 0x7f800000.  It stays on the device: no host synchronisation.
+ *   2. E = (pattern >> 23) - 126 is the smallest exponent with Gmax < 2^E that the pattern's exponent field gives.  With N = n_frames H
+ *      W (known on the host) and B its bit length (N < 2^B),  s = 60 - B - E  ( = 62 - (B + 2) - E ).  A texel receives at most 4 N
+ *      contributions, each |G_c omega_k| <= Gmax < 2^E since 0 <= omega_k <= 1, so every partial sum of the integers below is under
+ *      4 N 2^(E + s) < 2^(B + 2) 2^(60 - B) = 2^62: no overflow, whatever the order.  With s + 1 the same bound is >= 2^62.
+ *   3. A contribution is t = fl(G_c omega_k) in f64 (omega_k from bilinear_inl.h's four products; the product with G_c rounds once),
+ *      scaled by 2^s (exact: |s| <= 186, a power of two) and converted with round-to-nearest-even to an int64 q; q != 0 is added with
+ *      a no-return 64-bit INTEGER atomic into d_workspace, int64 [Ht][Wt][n_channels] (x n_frames for per-frame textures), which the
+ *      entry zeroes on the stream.  Contributions that are exactly 0 are skipped.
+ *   4. A fold kernel writes (float)((double)sum 2^-s).
+ * Integer addition is associative and commutative, so d_grad_tex is bit-identical from run to run, for any launch geometry, and
+ * for ANY PERMUTATION OF THE FRAMES (of a shared texture; per-frame textures permute with them).
+ * DEGENERATE Gmax.  Gmax = 0: d_grad_tex and d_grad_uv are all 0.  A NaN or an infinity ANYWHERE in d_grad_image: d_grad_tex is
+ * all NaN and d_grad_uv all 0 (nothing is accumulated: the conversion of a non-finite value to an integer is never reached).
+ * CONTRACT, with u = 2^-24, eps = 2^-53, kappa and M of the lookup, k_g = 6, and per texel element m = the number of its non-zero
+ * contributions and A = sum |G_c omega_k| over them:
+ *   (a) there is a cell K whose closed support is within delta of the exact clamped (x, y), the returned one, such that
+ *       |g^_u - g_u| <= u |g_u| + kappa Wt M sum_c |G_c|   with g_u = Wt sum_c G_c (d/du of K's patch at (x, y)); v alike with Ht; the
+ *       decision "the clamp is active" is exact for an unclamped x at least delta from 0 and Wt - 1 and either way inside;
+ *   (b) |g^ - g*| <= u |g*| + m 2^-(s + 1) + k_g eps A.
+ * Derivation.  (a): a derivative of K's patch is linear in the other coordinate with slope at most 4 M: 4 M delta for the move;
+ * differences of texels 1 eps, two products and a sum: below 8 eps M; the sum over the channels (n_channels + 1) eps more, the
+ * product with Wt one more: (4 delta + 14 eps) M Wt sum |G_c| <= 10 x 2^-50 P_x U Wt M sum |G_c|, inside kappa; the store's u.  (b):
+ * 1 - a and 1 - b round once, the weight's product once: omega^ within 3 eps of omega; the product with G_c: 4 eps |G_c omega_k|;
+ * the scaling is exact and the conversion moves each contribution by at most 1/2 unit of 2^-s: m 2^-(s + 1); the integer sum is
+ * exact; (double)sum rounds once when |sum| >= 2^53 (1 eps of at most A (1 + ...)), the product with 2^-s is exact, the store rounds
+ * once: u.  Together 5 eps A, stated as k_g = 6.  Against the exact positions (x, y) instead of the returned ones each omega moves by
+ * at most 2 delta: add 2 delta sum |G_c| over the texel's pixels.  In f32 terms: with N = 2^21 pixels of |G| <= 1, s = 38 and a
+ * texel hit by 10^4 pixels carries an absolute error below 2^-25 from the conversion: under the store's rounding of anything >= 1.
+ * Shape: one thread per pixel for the pass that adds.  Neighbouring pixels share cells under magnification, so the lanes of a wave
+ * first add their integers up over each RUN of consecutive lanes with the same cell (a segmented suffix sum by shuffles, exact:
+ * integers) and the run's first lane issues its 4 n_channels atomics; a wave without a covered pixel skips all of it.  The sums
+ * are the same bits as with one atomic per contribution (measured: DESIGN.md section 5, "Textures").
+ * Asynchronous on `stream`, NO host synchronisation.  Calls on one handle share one u32 of device state (Gmax): order them, as
+ * calls that share the render's workspace.  n_frames == 0, or both outputs NULL: a successful no-op.  BODYFIT_ERR_INVALID (nothing
+ * is launched): every case of bodyfit_raster_texture_device but those of d_image and d_tex, and with frames to write: NULL
+ * d_grad_image, d_grad_tex without d_workspace, d_grad_uv without d_tex (n_faces > 0), 2^39 texel elements or more.
+ * NOT BUILT: the term's normal equations, the C++ mirror header's entry.                                                      */
+int bodyfit_raster_texture_grad_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                       long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                       const void* d_tex /* may be NULL without d_grad_uv */, int tex_kind, int n_channels,
+                                       int tex_height, int tex_width, long long tex_frame_stride, int n_frames,
+                                       const float* d_grad_image, float* d_grad_uv /* may be NULL */,
+                                       float* d_grad_tex /* may be NULL */, long long* d_workspace /* may be NULL without d_grad_tex */,
+                                       void* stream);
 /* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster.hip): the coverage of a render as a smooth
  * function of the vertices, after Laine et al., "Modular Primitives for High-Performance Differentiable Rendering" (2020).  Only
  * COVERAGE carries a gradient here: how an attribute interpolates inside a face as its corners move is not part of it.
