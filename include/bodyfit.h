@@ -245,7 +245,20 @@ int bodyfit_evaluate_block_cached(bodyfit_problem* p, int kind, int index, const
                                   double* residuals, double** jacobians);
 
 /* ark::Avatar::update(): camera-frame joints [F][nJ][3] (f64) and cloud [F][V][3] (f32) for the
- * problem's frames at the given parameters; either output may be NULL.                       */
+ * problem's frames at the given parameters; either output may be NULL.
+ * PRECISION.  Joints (f64): 1e-11 max(1, M_f / 4) m, M_f the frame's largest |coordinate| in metres.  Cloud (f32), per
+ * frame, against the exact forward of the f64 inputs:   |cloud_fv - exact| <= B_f = 4 E_f,   with E_f the largest error over
+ * the frame's vertices of the stated arithmetic itself on that frame: blend coefficients vec(R_j - I) in f32 (the one-launch
+ * sweep: Rodrigues in f32 from the parameters rounded to f32, first-order branch at theta^2 <= 1e-20; the two-launch sweep:
+ * the f64 rotation rounded to f32), beta and the model's directions in f32; both operands split in bf16 hi + lo by
+ * round-to-nearest-even, hi.hi + hi.lo + lo.hi accumulated in f32; the skinning transforms s Rr0 [A_j | P_j - A_j Jc_j] +
+ * [0 | t] computed in f64 and rounded to f32; the blend of a vertex's <= 4 transforms and the 3 x 4 product in f32.
+ * tests/domain_cases.py (model_cloud) is that arithmetic in numpy and tabulates E_f; the factor 4 covers the order of the f32
+ * sums and fused against unfused products.  E_f is about 1.5 f32 ulps of the frame's largest coordinate (the translation is
+ * inside the transform: 6e-7 m at 3 m, 1.6e-5 m at 100 m) plus about 2^-19 |s| (sum_k |feat_k| |posedirs_vk| + sum_k |beta_k|
+ * |shapedirs_vk|) (3.6e-6 m at |beta| = 5; 8.5e-5 m at theta = pi, |beta| = 5, s = 20, t_z = 60).  For |t| <= 4 m, s <= 1.4,
+ * |beta| ~ 1 this is the 5e-6 m the contract used to state in metres alone.  The clouds of the two sweeps lie within 2 B_f
+ * of each other (2e-6 m on such inputs).                                                                              */
 int bodyfit_forward(bodyfit_problem* p, const double* frame_params, const double* beta,
                     double* joints, float* cloud);
 
@@ -270,6 +283,13 @@ int bodyfit_forward_device(bodyfit_problem* p, const double* d_frame_params, con
  * operand block on the model's first VJP: that first call synchronises once), so it leaves the sweep buffers alone.
  * Deterministic: no atomics, fixed summation orders; a frame's rows depend on that frame only (bit-identical whatever F).
  * Without d_grad_cloud only the f64 chain kernel runs (problems without want_mesh included).
+ * PRECISION, per entry (frame f, column c), with S_fc = sum_i |G_fi| |dcloud_fi / dx_c| + sum |H| |djoints / dx_c|: within
+ * 2^-14 S_fc of the exact gradient with d_grad_cloud (each operand of the bf16 hi + lo split carries 16 significant bits, a
+ * product term is off by at most 2^-15 relative; a factor 2 for the f32 accumulation and the f32 skinning adjoint), within
+ * 1e-9 S_fc without it (f64 throughout) -- and also within 1e-4 (1e-7) of the frame's largest entry.  One exception, by
+ * design: a rotation with 0 < theta^2 <= DBL_EPSILON takes R = I + [a]x and dR_c = [e_c]x (the reference's Ceres branch;
+ * sweep, VJP and JVP alike), which is off the exponential's derivative by up to 2 theta <= 3e-8 per entry: the three columns
+ * of such a rotation carry up to 2 theta D_f sum |H_f| more, D_f the diameter of the posed skeleton in metres.
  * BODYFIT_ERR_INVALID: NULL problem / parameters / d_grad_frame_params, grad_cloud without want_mesh or with a row
  * shorter than 3 V, d_grad_beta missing with n_cols = 76 + nS.                                                          */
 int bodyfit_forward_vjp_device(bodyfit_problem* p, const double* d_frame_params, const double* d_beta,
@@ -288,7 +308,8 @@ int bodyfit_forward_vjp(bodyfit_problem* p, const double* frame_params, const do
  * under the problem's use_shape / pose_blend / beta_per_frame and its fixed R0 (without pose_blend the pose features carry no
  * tangent, without use_shape beta carries none).  With the 76 + nS unit tangents the outputs are the dense Jacobian.
  * Tolerances (against central differences of the f64 forward): joints <= 1e-7, cloud <= 1e-4 of the largest entry of that
- * (frame, tangent)'s tangent; the chain is f64, the blend tangent runs on the matrix pipe like the forward's blend (bf16 hi/lo
+ * (frame, tangent)'s tangent (unit tangents included: every column of the Jacobian to its own scale; the joints' plus
+ * 2 theta D_f on the columns of a rotation in the first-order branch, see bodyfit_forward_vjp_device); the chain is f64, the blend tangent runs on the matrix pipe like the forward's blend (bf16 hi/lo
  * split, f32 accumulation) and the skinning tangent is f32.
  * Deterministic: no atomics, fixed summation orders; the outputs of (frame, tangent) depend on that frame's parameters and that
  * tangent only (bit-identical whatever F and K and wherever the tangent sits); a zero tangent gives exactly 0.

@@ -172,15 +172,16 @@ def kp_ids(v: Variant):
     return np.arange(v.n_joints + len(v.model.landmark_vid), dtype=np.int32)
 
 
-def observations(v: Variant, F, seed=0, ids_=None, ragged=True):
+def observations(v: Variant, F, seed=0, ids_=None, ragged=True, empty=None):
     """keypoint observations for any joint count: random pixels around the image centre (a parity test compares residuals
-    and Jacobians, it needs no true observation), some frames ragged, one empty"""
+    and Jacobians, it needs no true observation), some frames ragged, one empty (every seventh from frame 3 on; `empty`: the
+    frames to leave empty instead)"""
     rng = np.random.default_rng(seed)
     ids_ = kp_ids(v) if ids_ is None else np.asarray(ids_, np.int32)
     off, kid, uv = [0], [], []
     for f in range(F):
         keep = rng.uniform(size=len(ids_)) > (0.2 if ragged else -1.0)
-        if ragged and f % 7 == 3:
+        if ragged and (f % 7 == 3 if empty is None else f in empty):
             keep[:] = False
         kid.append(ids_[keep])
         uv.append(rng.uniform([200.0, 100.0], [1700.0, 1000.0], size=(int(keep.sum()), 2)))

@@ -4,13 +4,15 @@ f64 checker; and the shapes bodyfit_model_create / bodyfit_problem_create refuse
 
 Bounds are those of the SMPL-shape tests: residuals 1e-9 px and the Jacobian 1e-9 of its largest entry
 (test_gpu_parity.py), joints 1e-11 m and the f32 cloud 5e-6 m (test_mesh_forward_matches_oracle), one launch against two
-at the bounds of test_gpu_one_launch.py, the VJP at 1e-4 of each frame's largest entry (test_gpu_forward_vjp.py) plus a
-per-column bound (test_vjp_matches_checker_on_every_shape)."""
+at the bounds of test_gpu_one_launch.py, the VJP at 1e-4 of each frame's largest entry (test_gpu_forward_vjp.py) plus two
+per-column bounds: against the column's largest entry over the frames (test_vjp_matches_checker_on_every_shape) and, entry by
+entry, 2^-14 S_fc + CD_fc (joints only: 1e-9 S_fc; tests/domain_cases.py)."""
 import importlib
 
 import numpy as np
 import pytest
 
+import domain_cases as dc
 import model_variants as mv
 from test_gpu_fit import TOL, gauge_free_diff
 from test_gpu_one_launch import _Env, _timeouts
@@ -196,12 +198,15 @@ def test_vjp_matches_checker_on_every_shape(oracle_mod, vid, F):
     prob = _kp_free(gm, F, R0, n_cols=76 + nS, use_shape=nS > 0, beta_per_frame=per_frame, want_mesh=True)
     gx, gb = prob.forward_vjp(x, beta, G, H)
     b_ref = beta if beta is not None else np.zeros(1)
-    gx_ref, gb_ref = mv.ref_grad(om, x, b_ref, R0, G, H, nS > 0, v.pose_blend_data, per_frame, nS > 0)
+    ref = dc.ref_grad_scaled(om, x, b_ref, R0, G, H, nS > 0, v.pose_blend_data, per_frame, nS > 0)   # (mv.ref_grad's numbers)
+    gx_ref, gb_ref = ref.gx, ref.gb
     _check_vjp(gx, gx_ref)
+    dc.check_columns(gx, gx_ref, ref.Sx, ref.CDx, what=f"vjp {vid} F={F} dL/dx")           # 2^-14 S_fc + CD_fc
     if nS == 0:
         assert gb is None
     else:
         _check_vjp(gb, gb_ref, np.abs(gx_ref).max(1).sum() if not per_frame else np.abs(gx_ref).max(1))
+        dc.check_columns(gb, gb_ref, ref.Sb, ref.CDb, what=f"vjp {vid} F={F} dL/dbeta")
     gx2, gb2 = prob.forward_vjp(x, beta, G, H)
     assert np.array_equal(gx, gx2) and (gb is None or np.array_equal(gb, gb2))
     if F > 1:
@@ -229,6 +234,13 @@ def test_joints_only_vjp_matches_checker(oracle_mod, vid, F):
     gx_ref, gb_ref = mv.ref_grad(om, x, beta, R0, None, H, True, v.pose_blend_data, False, True)
     _check_vjp(gx, gx_ref)
     _check_vjp(gb, gb_ref, np.abs(gx_ref).max(1).sum())
+    # per column, f64: 1e-9 S_fc against fourth-order differences at t = 0 (tests/test_gpu_domain.py, _check_vjp)
+    ref4 = dc.ref_grad_scaled(om, x, beta, R0, None, H, True, v.pose_blend_data, False, True, step=1e-3, order=4, zero_t=True)
+    f64 = dict(rel=1e-9, add_cd=False, ref_share=0.5)
+    # (random_params puts a joint at theta^2 just below DBL_EPSILON: the first-order Rodrigues branch, dR 2 theta off)
+    dc.check_columns(gx, ref4.gx, ref4.Sx, ref4.CDx, what=f"joints-only vjp {vid} F={F} dL/dx",
+                     slack=dc.first_order_slack(om, x, beta, R0, H, True, v.pose_blend_data), **f64)
+    dc.check_columns(gb, ref4.gb, ref4.Sb, ref4.CDb, what=f"joints-only vjp {vid} F={F} dL/dbeta", **f64)
     gx2, gb2 = prob.forward_vjp(x, beta, None, H)
     assert np.array_equal(gx, gx2) and np.array_equal(gb, gb2)
 

@@ -6,7 +6,7 @@ part of the vertex's blended skinning transform, cloud_d = cloud0 + L d.  Deriva
 (step 1e-6) of  checker cloud(x, beta) + L(x) d,  dL/dd against the exact sum_f L_fv^T G_fv.  Bounds (u = 2^-24) are the header's:
   forward       |cloud_d - cloud0 - L d| <= u (16 |s| |d_v|_1 + |cloud_d|), both clouds from the device
   dL/dd         <= u (16 sum_f |s_f| |G_fv|_1 + |dL/dd|)
-  dL/dx, dL/dbeta   1e-4 of the row's largest entry (tests/test_gpu_forward_vjp.py)
+  dL/dx, dL/dbeta   1e-4 of the row's largest entry (tests/test_gpu_forward_vjp.py) and, entry by entry, 2^-14 S_fc + CD_fc
   JVP           cloud 1e-4, joints 1e-7 of the (frame, tangent)'s largest entry (tests/test_gpu_forward_jvp.py)
   Laplacian     <= u |l| + 2^-48 sum |x| over the vertex and its ring
 
@@ -18,6 +18,7 @@ import importlib
 import numpy as np
 import pytest
 
+import domain_cases as dc
 import gram_ref
 import model_variants as mv
 import offsets_ref as ref
@@ -192,11 +193,30 @@ def _delta_part_gx(m, x, R0, G, d):
     return gx
 
 
-def _check_rows(g, g_ref, tol, what):
+def _delta_cloud(m, x, R0, d):
+    """L(x) d [F, V, 3] with the skinning weights as a sparse matrix (offsets_ref.delta(blend_matrices(...)), fast enough to be
+    differenced column by column)"""
+    from scipy.sparse import csr_matrix
+    F = x.shape[0]
+    W = csr_matrix(np.asarray(m.weights, np.float64))
+    dd = np.broadcast_to(d.astype(np.float64), (F,) + d.shape[-2:])
+    out = np.empty((F, W.shape[0], 3))
+    for f in range(F):
+        A = ref.chain_rotations(m.parent, x[f])
+        M = x[f, 0] * ref.rodrigues(x[f, 1:4]) @ R0[f]
+        BA = (W @ A.reshape(len(A), 9)).reshape(-1, 3, 3)
+        out[f] = np.einsum("vbc,vc->vb", BA, dd[f]) @ M.T
+    return out
+
+
+def _check_rows(g, g_ref, tol, what, S=None, CD=None):
+    """every entry within tol of its frame's largest entry, AND (S given) within 2^-14 S_fc + CD_fc of its own scale"""
     for f in range(g_ref.shape[0]):
         scale = np.abs(g_ref[f]).max()
         err = np.abs(g[f] - g_ref[f]).max()
         assert err <= tol * scale, (what, f, err, scale, int(np.abs(g[f] - g_ref[f]).argmax()))
+    if S is not None:
+        dc.check_columns(g, g_ref, S, CD, what="offsets " + what)
 
 
 @pytest.mark.parametrize("name,F,per_off,pose_blend,per_beta", DERIV_CASES, ids=DERIV_IDS)
@@ -210,11 +230,17 @@ def test_vjp_against_central_differences(api, synth, models, name, F, per_off, p
     assert go.dtype == np.float32 and go.shape == d.shape
     gx_ref, gb_ref = mv.ref_grad(c["om"], x, beta, R0, G, H, True, pose_blend, per_beta, True)
     gx_ref = gx_ref + _delta_part_gx(m, x, R0, G, d)       # (beta does not enter L: dL/dbeta's reference is the checker's alone)
-    _check_rows(gx, gx_ref, 1e-4, "dL/dx")
+    # the same gradient with every entry's scale S_fc and the differences' own error CD_fc: the displaced cloud, checker's cloud
+    # + L(x) d, differenced as a whole
+    sc = dc.ref_grad_scaled(c["om"], x, beta, R0, G, H, True, pose_blend, per_beta, True,
+                            cloud_extra=lambda xx: _delta_cloud(m, xx, R0, d))
+    assert np.abs(sc.gx - gx_ref).max() <= 1e-7 * np.abs(gx_ref).max()       # (the two references are one)
+    _check_rows(gx, gx_ref, 1e-4, "dL/dx", sc.Sx, sc.CDx)
     if per_beta:
-        _check_rows(gb, gb_ref, 1e-4, "dL/dbeta")
+        _check_rows(gb, gb_ref, 1e-4, "dL/dbeta", sc.Sb, sc.CDb)
     else:
         assert np.abs(gb - gb_ref).max() <= 1e-4 * np.abs(gb_ref).max()
+        dc.check_columns(gb, gb_ref, sc.Sb, sc.CDb, what="offsets dL/dbeta (shared)")
     # the offsets moved the gradient by more than the tolerance: the check above would see a VJP that ignored them
     gx0, _ = c["prob"].forward_vjp(x, beta, G, H)
     assert np.abs(gx - gx0).max() > 1e-3 * np.abs(gx_ref).max()
