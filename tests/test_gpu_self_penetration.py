@@ -1,5 +1,5 @@
 """GPU: the torch layer over the winding number: vertex_winding, vertex_normals, winding_number, signed_distance and
-SelfPenetrationTerm (torch_layer.py), on the two-sphere scene of tests/winding_ref.py — the unit icosphere A and the icosphere B of
+SelfPenetrationTerm (torch_layer/solid.py), on the two-sphere scene of tests/winding_ref.py — the unit icosphere A and the icosphere B of
 radius 0.7 about (1.2, 0, 0) as one mesh, 50 of 324 (202 of 1,284) vertices inside the other sphere.
 
 Reference: wr.self_penetration64 (f64: winding with the own faces left out, the oriented brute force with minus the vertex normal,
