@@ -313,6 +313,20 @@ def load_library():
                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                        C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+    lib.bodyfit_texture_mip_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.bodyfit_raster_texture_mip_build_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                            C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_raster_texture_mip_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                      C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_float),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_texture_mip_grad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                           C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                           C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -320,6 +334,30 @@ def load_library():
 def _check(rc):
     if rc != 0:
         raise BodyfitError(f"bodyfit status {rc}: {load_library().bodyfit_last_error().decode()}")
+
+
+def _background4(background):
+    """a float (every channel) or up to four floats as the host float[4] the lookups take"""
+    bg = np.zeros(4, np.float32)
+    b = np.atleast_1d(np.asarray(background, np.float32))
+    if b.ndim != 1 or b.shape[0] > 4:
+        raise ValueError("background is a float or up to four floats")
+    bg[:4 if b.shape[0] == 1 else b.shape[0]] = b
+    return bg
+
+
+TX_MAX_LEVELS = 15          # BODYFIT_TX_MAX_LEVELS
+
+
+def texture_mip_layout(tex_height: int, tex_width: int, max_level: int = -1):
+    """bodyfit_texture_mip_layout (host only): (n_levels, [(H_l, W_l)], [the texel offset of level l in the packed buffer of the
+    levels 1 .. n_levels - 1; entry 0 is 0 and not used], that buffer's texels)"""
+    n, total = C.c_int(0), C.c_longlong(0)
+    hs, ws, off = (C.c_int * TX_MAX_LEVELS)(), (C.c_int * TX_MAX_LEVELS)(), (C.c_longlong * TX_MAX_LEVELS)()
+    _check(load_library().bodyfit_texture_mip_layout(int(tex_height), int(tex_width), int(max_level), C.byref(n), hs, ws, off,
+                                                     C.byref(total)))
+    k = n.value
+    return k, [(hs[l], ws[l]) for l in range(k)], [off[l] for l in range(k)], total.value
 
 
 def _c64(a):
@@ -1134,6 +1172,49 @@ class Raster:
             self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_uv_ptr, int(n_uv), d_uv_faces_ptr, d_tex_ptr,
             int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames), d_grad_image_ptr,
             d_grad_uv_ptr, d_grad_tex_ptr, d_workspace_ptr, stream))
+
+    def texture_mip_build_device(self, d_tex_ptr: int | None, tex_kind: int, n_channels: int, tex_height: int, tex_width: int,
+                                 tex_frame_stride: int, n_textures: int, max_level: int, d_mip_ptr: int | None,
+                                 mip_frame_stride: int, stream: int | None = None):
+        """bodyfit_raster_texture_mip_build_device: the levels 1 .. n - 1 of n_textures textures into mip (f32, the packed
+        layout of texture_mip_layout, mip_frame_stride elements between the textures' pyramids), each level the f64 average
+        of the stored level below it.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_texture_mip_build_device(
+            self.h, d_tex_ptr, int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride),
+            int(n_textures), int(max_level), d_mip_ptr, int(mip_frame_stride), stream))
+
+    def texture_mip_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                           d_uv_ptr: int | None, n_uv: int, d_uv_faces_ptr: int | None, d_tex_ptr: int | None, tex_kind: int,
+                           n_channels: int, tex_height: int, tex_width: int, tex_frame_stride: int, n_frames: int, intr,
+                           d_mip_ptr: int | None, mip_frame_stride: int, max_level: int, lod_bias: float, background,
+                           d_image_ptr: int, d_weight_ptr: int | None = None, d_uv_out_ptr: int | None = None,
+                           d_lod_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_raster_texture_mip_device: texture_device with mipmaps: the level of detail L of every pixel from its
+        face's footprint under intr = (fx, fy, cx, cy) plus lod_bias, clamped to the pyramid's levels (mip: what
+        texture_mip_build_device wrote for the same max_level), and the trilinear blend of the levels floor(L) and
+        floor(L) + 1; lod [F, H, W] f32 (or None) receives L.  Where L = 0 the image is texture_device's bit for bit."""
+        bg = _background4(background)
+        _check(load_library().bodyfit_raster_texture_mip_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_uv_ptr, int(n_uv), d_uv_faces_ptr, d_tex_ptr,
+            int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames), float(intr[0]),
+            float(intr[1]), float(intr[2]), float(intr[3]), d_mip_ptr, int(mip_frame_stride), int(max_level), float(lod_bias),
+            bg.ctypes.data_as(C.POINTER(C.c_float)), d_image_ptr, d_weight_ptr, d_uv_out_ptr, d_lod_ptr, stream))
+
+    def texture_mip_grad_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                                d_uv_ptr: int | None, n_uv: int, d_uv_faces_ptr: int | None, d_tex_ptr: int | None, tex_kind: int,
+                                n_channels: int, tex_height: int, tex_width: int, tex_frame_stride: int, n_frames: int, intr,
+                                d_mip_ptr: int | None, mip_frame_stride: int, max_level: int, lod_bias: float,
+                                d_grad_image_ptr: int, d_grad_uv_ptr: int | None, d_grad_tex_ptr: int | None,
+                                d_workspace_ptr: int | None, stream: int | None = None):
+        """bodyfit_raster_texture_mip_grad_device: the gradients of texture_mip_device's image at the fixed level of detail:
+        grad_uv [F, H, W, 2] (or None) and grad_tex in the LEVEL-0 texture's layout (or None), the exact adjoint of "average
+        the pyramid, then filter", summed in the int64 workspace of (Ht Wt + total) n_channels elements per texture (level 0
+        first) and folded in a fixed order: bit-identical whatever the order of the pixels and of the frames."""
+        _check(load_library().bodyfit_raster_texture_mip_grad_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_uv_ptr, int(n_uv), d_uv_faces_ptr, d_tex_ptr,
+            int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames), float(intr[0]),
+            float(intr[1]), float(intr[2]), float(intr[3]), d_mip_ptr, int(mip_frame_stride), int(max_level), float(lod_bias),
+            d_grad_image_ptr, d_grad_uv_ptr, d_grad_tex_ptr, d_workspace_ptr, stream))
 
     def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_frame_stride: int, n_frames: int, invert: bool,
                         d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):

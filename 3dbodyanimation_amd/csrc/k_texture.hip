@@ -16,6 +16,8 @@
 //   k_tx_fold    one thread per texel element: (float)((double)sum 2^-s)
 // The scale exponent s = 60 - B - E, B the bit length of the pixel count (host) and E the smallest integer with max|G| < 2^E
 // (device): no host synchronisation.  No float atomics anywhere.
+// The lookup with mipmaps (bodyfit_raster_texture_mip_*: k_txm_build, k_txm_forward, k_txm_grad, k_txm_fold) stands below the
+// plain kernels, which it leaves as they are, and shares tx_pixel, k_tx_gmax and the scale exponent with them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -287,6 +289,318 @@ void tx_dispatch(int tex_kind, int C, Launch&& launch) {
 #undef TX_CASE
 }
 
+// ---- mipmaps: the pyramid, the lookup with a level of detail, its gradients (include/bodyfit.h, MIPMAPS OF THE TEXTURE LOOKUP) -------
+//   k_txm_build<T>   one thread per element of level l + 1: the average of its 4 (or 2) children of the STORED level l in f64,
+//                rounded once to f32.  One launch per level, plain stores.
+//   k_txm_forward<C, T>  tx_pixel's pixel, then the footprint from the face's projected corners (txm_lod), then one or two
+//                bilinear patches, each level with its own clamp and cell; where f = 0 only level l0 is read.
+//   k_txm_grad<C, T>  the same pixel and level again; (a) the levels' patch derivatives blended; (b) 4 C contributions to level l0
+//                and, where f != 0, 4 C to level l0 + 1, as integers into the packed int64 pyramid (level 0 first).
+//   k_txm_fold   one thread per level-0 texel element: the fixed-order gather over the levels.
+struct TxMip {
+  double fx, fy, cx, cy;
+  const float* mip;          // levels 1 .. n - 1, packed; per frame mip_stride elements apart (shared: 0)
+  long long mip_stride;
+  long long off[BODYFIT_TX_MAX_LEVELS];     // TEXEL offset of level l in the packed buffer (off[0] unused)
+  int Hl[BODYFIT_TX_MAX_LEVELS], Wl[BODYFIT_TX_MAX_LEVELS];
+  int n_levels;
+  float lod_bias;
+};
+
+// the layout (host): level l + 1 exists iff l < max_level, (H_l, W_l) != (1, 1) and each of H_l, W_l is even or 1
+int txm_layout(int Ht, int Wt, int max_level, int* Hl, int* Wl, long long* off, long long* total) {
+  int n = 1;
+  Hl[0] = Ht; Wl[0] = Wt; off[0] = 0;
+  long long at = 0;
+  while (n < BODYFIT_TX_MAX_LEVELS && (max_level < 0 || n <= max_level)) {
+    const int h = Hl[n - 1], w = Wl[n - 1];
+    if ((h == 1 && w == 1) || (h > 1 && (h & 1)) || (w > 1 && (w & 1))) break;
+    Hl[n] = h > 1 ? h / 2 : 1; Wl[n] = w > 1 ? w / 2 : 1;
+    off[n] = at;
+    at += (long long)Hl[n] * Wl[n];
+    ++n;
+  }
+  *total = at;
+  return n;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_txm_build(const T* __restrict__ src, long long src_stride, int Hs, int Ws, int C,
+                                                   float* __restrict__ dst, long long dst_stride, int Hd, int Wd, long long per_tex,
+                                                   long long total) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const long long tex = e / per_tex, r = e - tex * per_tex;       // r = (i Wd + j) C + c
+  const int c = (int)(r % C);
+  const long long ij = r / C;
+  const int i = (int)(ij / Wd), j = (int)(ij - (long long)i * Wd);
+  const T* s = src + tex * src_stride;
+  const int di = Hs > 1 ? 1 : 0, dj = Ws > 1 ? 1 : 0;             // a dimension of 1 stays 1
+  const size_t i0 = (size_t)(Hs > 1 ? 2 * i : 0), j0 = (size_t)(Ws > 1 ? 2 * j : 0);
+  double v;
+  if (di && dj) {
+    const double t00 = (double)s[(i0 * Ws + j0) * C + c], t01 = (double)s[(i0 * Ws + j0 + 1) * C + c];
+    const double t10 = (double)s[((i0 + 1) * Ws + j0) * C + c], t11 = (double)s[((i0 + 1) * Ws + j0 + 1) * C + c];
+    v = ((t00 + t01) + (t10 + t11)) * 0.25;
+  } else {
+    const double t0 = (double)s[(i0 * Ws + j0) * C + c], t1 = (double)s[((i0 + di) * Ws + j0 + dj) * C + c];
+    v = (t0 + t1) * 0.5;
+  }
+  dst[tex * dst_stride + r] = (float)v;
+}
+
+// The level of detail of a live pixel: L = clamp(log2(rho^2) / 2 + lod_bias, 0, n_levels - 1), rho^2 the largest eigenvalue of J J^T,
+// J = diag(Wt, Ht) d(uv)/d(sample) from the face's projected corners.  0 where rho^2, the area or a corner is not finite or A = 0.
+__device__ __forceinline__ double txm_lod(const TxArgs& A, const TxMip& M, long long o, const TxPixel& p) {
+  if (M.n_levels <= 1) return 0.0;
+  const int t = A.face_img[o];
+  const size_t frame = (size_t)(o / A.ppf);
+  const float* v = A.verts + frame * (size_t)A.verts_stride;
+  double px[3], py[3], Z[3], du[3], dv[3];
+  bool fin = true;
+  for (int a = 0; a < 3; ++a) {
+    const size_t id = (size_t)A.faces[3 * t + a];
+    const float X = v[3 * id], Y = v[3 * id + 1], Zf = v[3 * id + 2];
+    if (!(X - X == 0.0f) || !(Y - Y == 0.0f)) fin = false;
+    Z[a] = (double)Zf;                                       // (finite and > 0: tx_pixel's rule)
+    px[a] = M.fx * ((double)X / Z[a]) + M.cx;
+    py[a] = M.fy * ((double)Y / Z[a]) + M.cy;
+    const int k = A.uv_faces[3 * t + a];
+    du[a] = (double)A.uv[2 * (size_t)k] - p.u;
+    dv[a] = (double)A.uv[2 * (size_t)k + 1] - p.v;
+  }
+  if (!fin) return 0.0;
+  const double area = (px[1] - px[0]) * (py[2] - py[0]) - (px[2] - px[0]) * (py[1] - py[0]);
+  if (!(area != 0.0) || !(area - area == 0.0)) return 0.0;
+  const float l0 = A.bary[3 * (size_t)o], l1 = A.bary[3 * (size_t)o + 1], l2 = A.bary[3 * (size_t)o + 2];
+  const double S = ((double)l0 / Z[0] + (double)l1 / Z[1]) + (double)l2 / Z[2];      // tx_pixel's S, the same bits
+  double hx[3], hy[3];
+  for (int a = 0; a < 3; ++a) {
+    const int b = (a + 1) % 3, c = (a + 2) % 3;
+    hx[a] = ((py[b] - py[c]) / area) / Z[a];
+    hy[a] = ((px[c] - px[b]) / area) / Z[a];
+  }
+  const double ux = ((hx[0] * du[0] + hx[1] * du[1]) + hx[2] * du[2]) / S, uy = ((hy[0] * du[0] + hy[1] * du[1]) + hy[2] * du[2]) / S;
+  const double vx = ((hx[0] * dv[0] + hx[1] * dv[1]) + hx[2] * dv[2]) / S, vy = ((hy[0] * dv[0] + hy[1] * dv[1]) + hy[2] * dv[2]) / S;
+  const double j00 = (double)A.Wt * ux, j01 = (double)A.Wt * uy, j10 = (double)A.Ht * vx, j11 = (double)A.Ht * vy;
+  const double ca = j00 * j00 + j10 * j10, cb = j01 * j01 + j11 * j11, cc = j00 * j01 + j10 * j11;
+  const double hs = 0.5 * (ca + cb), hd = 0.5 * (ca - cb);
+  const double rho2 = hs + sqrt(hd * hd + cc * cc);
+  if (!(rho2 - rho2 == 0.0)) return 0.0;
+  const double Lr = 0.5 * log2(rho2) + (double)M.lod_bias;
+  const double top = (double)(M.n_levels - 1);
+  const double Lc = !(Lr > 0.0) ? 0.0 : (Lr > top ? top : Lr);      // (a NaN, from -inf + inf, is 0 as well)
+  return (double)(float)Lc;          // d_lod's f32 IS the L that is used: the gradients' contracts are stated at the returned L
+}
+
+// one level's clamp (tx_pixel's, with the level's size) and cell
+struct TxmLevel {
+  bool free_x, free_y;
+  bodyfit::BilinearCell cell;
+};
+
+__device__ __forceinline__ TxmLevel txm_level(const TxPixel& p, int Wl, int Hl) {
+  TxmLevel r;
+  const double xr = p.u * (double)Wl - 0.5, yr = p.v * (double)Hl - 0.5;
+  const double xmax = (double)(Wl - 1), ymax = (double)(Hl - 1);
+  r.free_x = xr >= 0.0 && xr <= xmax;
+  r.free_y = yr >= 0.0 && yr <= ymax;
+  const double x = xr < 0.0 ? 0.0 : (xr > xmax ? xmax : xr);
+  const double y = yr < 0.0 ? 0.0 : (yr > ymax ? ymax : yr);
+  r.cell = bodyfit::bilinear_cell(x, y, Wl, Hl);
+  return r;
+}
+
+// value and derivatives of level l's patch at the pixel (level 0: the texture in its own type; l > 0: the f32 pyramid)
+template <int C, typename T>
+__device__ __forceinline__ void txm_patch(const TxArgs& A, const TxMip& M, const T* tex, size_t frame, int l, const TxmLevel& lv,
+                                          double* val, double* du, double* dv) {
+  if (l == 0) bodyfit::bilinear_patch<C, T>(tex + frame * (size_t)A.tex_stride, A.Wt, lv.cell, val, du, dv);
+  else bodyfit::bilinear_patch<C, float>(M.mip + frame * (size_t)M.mip_stride + (size_t)M.off[l] * C, M.Wl[l], lv.cell, val, du, dv);
+}
+
+template <int C, typename T>
+__global__ __launch_bounds__(256) void k_txm_forward(TxArgs A, TxMip M, const T* __restrict__ tex, float4 bg,
+                                                     float* __restrict__ image, float* __restrict__ weight,
+                                                     float* __restrict__ uv_out, float* __restrict__ lod) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o >= A.total) return;
+  const TxPixel p = tx_pixel(A, o);
+  const float bgc[4] = {bg.x, bg.y, bg.z, bg.w};
+  float out[C];
+  for (int c = 0; c < C; ++c) out[c] = bgc[c];
+  double L = 0.0;
+  if (p.ok) {
+    const size_t frame = (size_t)(o / A.ppf);
+    L = txm_lod(A, M, o, p);
+    const int l0 = (int)floor(L);
+    const double f = L - (double)l0;
+    double val[C];
+    txm_patch<C, T>(A, M, tex, frame, l0, txm_level(p, M.Wl[l0], M.Hl[l0]), val, nullptr, nullptr);
+    if (f != 0.0) {
+      double val1[C];
+      txm_patch<C, T>(A, M, tex, frame, l0 + 1, txm_level(p, M.Wl[l0 + 1], M.Hl[l0 + 1]), val1, nullptr, nullptr);
+      const double nf = 1.0 - f;
+      for (int c = 0; c < C; ++c) val[c] = nf * val[c] + f * val1[c];
+    }
+    for (int c = 0; c < C; ++c) out[c] = (float)val[c];
+  }
+  for (int c = 0; c < C; ++c) image[C * (size_t)o + c] = out[c];
+  if (weight)
+    for (int k = 0; k < 3; ++k) weight[3 * (size_t)o + k] = (float)p.w[k];
+  if (uv_out) { uv_out[2 * (size_t)o] = (float)p.u; uv_out[2 * (size_t)o + 1] = (float)p.v; }
+  if (lod) lod[o] = (float)L;
+}
+
+// BODYFIT_TXM_COMBINE = 1: k_tx_grad's run combining with the key (level, cell) of BOTH levels of the lane.  The same bits either
+// way (integers); measured both ways, magnified and minified ("Mipmaps"): combining is the faster in both, and the default.
+#ifndef BODYFIT_TXM_COMBINE
+#define BODYFIT_TXM_COMBINE 1
+#endif
+
+template <int C, typename T>
+__global__ __launch_bounds__(256) void k_txm_grad(TxArgs A, TxMip M, const T* __restrict__ tex, const float* __restrict__ grad_image,
+                                                  const unsigned* __restrict__ gmax, int B, long long pyramid,
+                                                  float* __restrict__ grad_uv, unsigned long long* __restrict__ sums) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool in = o < A.total;       // (no early return: with BODYFIT_TXM_COMBINE every lane of the wave reaches the shuffles)
+  const unsigned gbits = *gmax;
+  double gu = 0.0, gv = 0.0;
+  long long q[8][C];                 // 0 .. 3: level l0's texels, 4 .. 7: level l0 + 1's
+  for (int k = 0; k < 8; ++k)
+    for (int c = 0; c < C; ++c) q[k][c] = 0;
+  long long key0 = -1, key1 = -1;    // the lane's cells in the packed pyramid (with its frame, for per-frame textures); -1: none
+  size_t at[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (in && gbits != 0u && gbits < 0x7f800000u) {
+    const TxPixel p = tx_pixel(A, o);
+    if (p.ok) {
+      const size_t frame = (size_t)(o / A.ppf);
+      const double L = txm_lod(A, M, o, p);
+      const int l0 = (int)floor(L);
+      const double f = L - (double)l0, nf = 1.0 - f;
+      const int n_lv = f != 0.0 ? 2 : 1;
+      double G[C];
+      for (int c = 0; c < C; ++c) G[c] = (double)grad_image[C * (size_t)o + c];
+      const double scale = ldexp(1.0, tx_scale_exponent(gbits, B));
+      const size_t f0 = A.tex_stride ? frame * (size_t)pyramid * C : 0;
+      // (a constant trip count, unrolled: q and at are indexed with compile-time constants and stay in registers)
+#pragma unroll
+      for (int n = 0; n < 2; ++n) {
+        if (n >= n_lv) break;
+        const int l = l0 + n, Wl = M.Wl[l], Hl = M.Hl[l];
+        const TxmLevel lv = txm_level(p, Wl, Hl);
+        if (grad_uv) {
+          double val[C], du[C], dv[C];
+          txm_patch<C, T>(A, M, tex, frame, l, lv, val, du, dv);
+          double su = 0.0, sv = 0.0;
+          for (int c = 0; c < C; ++c) {
+            const double tu = G[c] * du[c], tv = G[c] * dv[c];
+            su = c == 0 ? tu : su + tu;
+            sv = c == 0 ? tv : sv + tv;
+          }
+          const double lu = lv.free_x ? su * (double)Wl : 0.0, lw = lv.free_y ? sv * (double)Hl : 0.0;
+          if (n_lv == 1) { gu = lu; gv = lw; }
+          else if (n == 0) { gu = nf * lu; gv = nf * lw; }
+          else { gu = gu + f * lu; gv = gv + f * lw; }
+        }
+        if (sums) {
+          double w[4];
+          bodyfit::bilinear_weights(lv.cell, w);
+          const size_t base = f0 + (l == 0 ? (size_t)0 : ((size_t)A.Ht * A.Wt + (size_t)M.off[l]) * C);
+          const bodyfit::BilinearCell& k = lv.cell;
+          at[4 * n + 0] = base + ((size_t)k.i0 * Wl + k.j0) * C; at[4 * n + 1] = base + ((size_t)k.i0 * Wl + k.j1) * C;
+          at[4 * n + 2] = base + ((size_t)k.i1 * Wl + k.j0) * C; at[4 * n + 3] = base + ((size_t)k.i1 * Wl + k.j1) * C;
+          (n == 0 ? key0 : key1) = (long long)at[4 * n];
+          const double share = n == 0 ? nf : f;
+          for (int kk = 0; kk < 4; ++kk) {
+            const double wk = n_lv == 1 ? w[kk] : share * w[kk];     // (f = 0: the plain entry's contribution, operation for operation)
+            for (int c = 0; c < C; ++c) {
+              const double tt = G[c] * wk;           // rounds once
+              q[4 * n + kk][c] = llrint(tt * scale); // exact scaling, round to nearest
+            }
+          }
+        }
+      }
+    }
+  }
+  bool issue = key0 >= 0;
+#if BODYFIT_TXM_COMBINE
+  if (sums && __ballot(key0 >= 0) != 0ull) {
+    const int lane = threadIdx.x & 63;
+    const long long prev0 = __shfl_up(key0, 1, 64), prev1 = __shfl_up(key1, 1, 64);
+    const bool head = lane == 0 || prev0 != key0 || prev1 != key1;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long later = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int run_end = later ? lane + 1 + __ffsll((long long)later) - 1 : 64;
+    for (int d = 1; d < 64; d <<= 1) {
+      const bool take = lane + d < run_end;
+      for (int k = 0; k < 8; ++k)
+        for (int c = 0; c < C; ++c) {
+          const long long other = __shfl_down(q[k][c], d, 64);
+          if (take) q[k][c] += other;
+        }
+    }
+    issue = head && key0 >= 0;
+  }
+#endif
+  if (issue)
+    for (int k = 0; k < 8; ++k)
+      for (int c = 0; c < C; ++c)
+        if (q[k][c] != 0) atomicAdd(sums + at[k] + c, (unsigned long long)q[k][c]);     // (no-return)
+  if (in && grad_uv) { grad_uv[2 * (size_t)o] = (float)gu; grad_uv[2 * (size_t)o + 1] = (float)gv; }
+}
+
+// One thread per level-0 texel element: sum_l (double)S_l[i_l][j_l][c] 2^-s a_l in the order l = 0, 1, ..., a_l the exact product of
+// the 1/4 (both dimensions halved) and 1/2 (one of them) factors; (i_l, j_l) the ancestor of (i, j) on level l.
+__global__ __launch_bounds__(256) void k_txm_fold(const unsigned long long* __restrict__ sums, TxMip M, int C, long long pyramid,
+                                                  long long n, const unsigned* __restrict__ gmax, int B,
+                                                  float* __restrict__ grad_tex) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const unsigned gbits = *gmax;
+  if (gbits >= 0x7f800000u) { grad_tex[e] = __uint_as_float(0x7fc00000u); return; }
+  const long long per = (long long)M.Hl[0] * M.Wl[0] * C;
+  const long long tex = e / per, r = e - tex * per;
+  const int c = (int)(r % C);
+  const long long ij = r / C;
+  int i = (int)(ij / M.Wl[0]), j = (int)(ij - (long long)i * M.Wl[0]);
+  const double unit = ldexp(1.0, -tx_scale_exponent(gbits, B));
+  const unsigned long long* s = sums + tex * pyramid * C;
+  double acc = (double)(long long)s[r] * unit;
+  double al = 1.0;
+  for (int l = 1; l < M.n_levels; ++l) {
+    const bool hi = M.Hl[l - 1] > 1, hj = M.Wl[l - 1] > 1;
+    if (hi) i >>= 1;
+    if (hj) j >>= 1;
+    al = al * (hi && hj ? 0.25 : 0.5);
+    const size_t idx = (((size_t)M.Hl[0] * M.Wl[0] + (size_t)M.off[l]) + ((size_t)i * M.Wl[l] + j)) * C + c;
+    acc = acc + ((double)(long long)s[idx] * unit) * al;
+  }
+  grad_tex[e] = (float)acc;
+}
+
+// the arguments the mip entries add to tx_check's; n_levels > 1 needs the pyramid
+int txm_check(const char* fn, double fx, double fy, double cx, double cy, float lod_bias, int n_levels, long long total,
+              int n_channels, const float* d_mip, long long tex_frame_stride, long long mip_frame_stride) {
+  if (!(fx > 0.0) || !(fy > 0.0) || !(fx - fx == 0.0) || !(fy - fy == 0.0) || !(cx - cx == 0.0) || !(cy - cy == 0.0))
+    return tx_invalid(fn, "fx or fy <= 0 or a non-finite intrinsic");
+  if (lod_bias != lod_bias) return tx_invalid(fn, "lod_bias is NaN");
+  if (n_levels > 1 && !d_mip) return tx_invalid(fn, "d_mip is NULL with more than one level");
+  if (n_levels > 1 && tex_frame_stride != 0 && mip_frame_stride < total * n_channels)
+    return tx_invalid(fn, "mip_frame_stride below the layout's total");
+  return BODYFIT_OK;
+}
+
+TxMip txm_args(double fx, double fy, double cx, double cy, const float* d_mip, long long tex_frame_stride, long long mip_frame_stride,
+               int tex_height, int tex_width, int max_level, float lod_bias, long long* total) {
+  TxMip M;
+  M.fx = fx; M.fy = fy; M.cx = cx; M.cy = cy; M.mip = d_mip; M.mip_stride = tex_frame_stride ? mip_frame_stride : 0;
+  for (int l = 0; l < BODYFIT_TX_MAX_LEVELS; ++l) { M.Hl[l] = M.Wl[l] = 1; M.off[l] = 0; }
+  M.n_levels = txm_layout(tex_height, tex_width, max_level, M.Hl, M.Wl, M.off, total);
+  M.lod_bias = lod_bias;
+  return M;
+}
+
 }  // namespace
 
 extern "C" {
@@ -358,6 +672,158 @@ int bodyfit_raster_texture_grad_device(bodyfit_raster* r, const int32_t* d_face,
   });
   if (d_grad_tex)
     BODYFIT_LAUNCH(k_tx_fold, dim3((unsigned)((n_tex + 255) / 256)), dim3(256), 0, st, sums, n_tex, V.d_scratch, B, d_grad_tex);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_texture_mip_layout(int tex_height, int tex_width, int max_level, int* n_levels, int* heights, int* widths,
+                               long long* offsets, long long* total) {
+  const char* fn = "bodyfit_texture_mip_layout";
+  if (tex_height < 1 || tex_width < 1 || tex_height > 16384 || tex_width > 16384)
+    return tx_invalid(fn, "texture size outside 1 .. 16384");
+  if (!n_levels) return tx_invalid(fn, "n_levels is NULL");
+  int Hl[BODYFIT_TX_MAX_LEVELS], Wl[BODYFIT_TX_MAX_LEVELS];
+  long long off[BODYFIT_TX_MAX_LEVELS], tot = 0;
+  const int n = txm_layout(tex_height, tex_width, max_level, Hl, Wl, off, &tot);
+  *n_levels = n;
+  for (int l = 0; l < n; ++l) {
+    if (heights) heights[l] = Hl[l];
+    if (widths) widths[l] = Wl[l];
+    if (offsets) offsets[l] = off[l];
+  }
+  if (total) *total = tot;
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_texture_mip_build_device(bodyfit_raster* r, const void* d_tex, int tex_kind, int n_channels, int tex_height,
+                                            int tex_width, long long tex_frame_stride, int n_textures, int max_level, float* d_mip,
+                                            long long mip_frame_stride, void* stream) {
+  const char* fn = "bodyfit_raster_texture_mip_build_device";
+  if (!r) return tx_invalid(fn, "handle is NULL");
+  if (n_textures < 0) return tx_invalid(fn, "negative n_textures");
+  if (n_channels < 1 || n_channels > 4) return tx_invalid(fn, "n_channels outside 1 .. 4");
+  if (tex_kind != 0 && tex_kind != 1) return tx_invalid(fn, "tex_kind must be 0 (u8) or 1 (f32)");
+  if (tex_height < 1 || tex_width < 1 || tex_height > 16384 || tex_width > 16384)
+    return tx_invalid(fn, "texture size outside 1 .. 16384");
+  TxMip M;
+  long long total = 0;
+  M.n_levels = txm_layout(tex_height, tex_width, max_level, M.Hl, M.Wl, M.off, &total);
+  if (n_textures > 1 && tex_frame_stride < (long long)tex_height * tex_width * n_channels)
+    return tx_invalid(fn, "tex_frame_stride below Ht Wt n_channels");
+  if (n_textures > 1 && M.n_levels > 1 && mip_frame_stride < total * n_channels)
+    return tx_invalid(fn, "mip_frame_stride below the layout's total");
+  if (n_textures == 0 || M.n_levels == 1) return BODYFIT_OK;
+  if (!d_tex || !d_mip) return tx_invalid(fn, "d_tex or d_mip is NULL");
+  if (total * n_channels * n_textures >= (1ll << 39)) return tx_invalid(fn, "2^39 pyramid elements or more in one call");
+  const bodyfit::RasterView V = bodyfit::raster_view(r);
+  HIP_TRY(hipSetDevice(V.device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int C = n_channels;
+  for (int l = 1; l < M.n_levels; ++l) {
+    const long long per = (long long)M.Hl[l] * M.Wl[l] * C, n = per * n_textures;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    float* dst = d_mip + M.off[l] * C;
+    if (l == 1 && tex_kind == 0)
+      BODYFIT_LAUNCH(k_txm_build<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t*>(d_tex), tex_frame_stride, M.Hl[0],
+                     M.Wl[0], C, dst, mip_frame_stride, M.Hl[1], M.Wl[1], per, n);
+    else if (l == 1)
+      BODYFIT_LAUNCH(k_txm_build<float>, grid, dim3(256), 0, st, static_cast<const float*>(d_tex), tex_frame_stride, M.Hl[0], M.Wl[0],
+                     C, dst, mip_frame_stride, M.Hl[1], M.Wl[1], per, n);
+    else
+      BODYFIT_LAUNCH(k_txm_build<float>, grid, dim3(256), 0, st, static_cast<const float*>(d_mip + M.off[l - 1] * C), mip_frame_stride,
+                     M.Hl[l - 1], M.Wl[l - 1], C, dst, mip_frame_stride, M.Hl[l], M.Wl[l], per, n);
+  }
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_texture_mip_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                      long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                      const void* d_tex, int tex_kind, int n_channels, int tex_height, int tex_width,
+                                      long long tex_frame_stride, int n_frames, double fx, double fy, double cx, double cy,
+                                      const float* d_mip, long long mip_frame_stride, int max_level, float lod_bias,
+                                      const float* background, float* d_image, float* d_weight, float* d_uv_out, float* d_lod,
+                                      void* stream) {
+  const char* fn = "bodyfit_raster_texture_mip_device";
+  bool work = false;
+  if (int rc = tx_check(fn, r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_kind, n_channels,
+                        tex_height, tex_width, tex_frame_stride, n_frames, &work))
+    return rc;
+  long long total = 0;
+  const TxMip M = txm_args(fx, fy, cx, cy, d_mip, tex_frame_stride, mip_frame_stride, tex_height, tex_width, max_level, lod_bias,
+                           &total);
+  if (int rc = txm_check(fn, fx, fy, cx, cy, lod_bias, M.n_levels, total, n_channels, d_mip, tex_frame_stride, mip_frame_stride))
+    return rc;
+  if (!work) return BODYFIT_OK;
+  if (!d_image) return tx_invalid(fn, "d_image is NULL");
+  const bodyfit::RasterView V = bodyfit::raster_view(r);
+  if (V.nF > 0 && !d_tex) return tx_invalid(fn, "d_tex is NULL");
+  HIP_TRY(hipSetDevice(V.device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+                           tex_frame_stride, n_frames);
+  const float4 bg = background ? make_float4(background[0], background[1], background[2], background[3])
+                               : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const dim3 grid((unsigned)((A.total + 255) / 256));
+  tx_dispatch(tex_kind, n_channels, [&](auto c, auto* type) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(type)>>;
+    BODYFIT_LAUNCH((k_txm_forward<decltype(c)::value, T>), grid, dim3(256), 0, st, A, M, static_cast<const T*>(d_tex), bg, d_image,
+                   d_weight, d_uv_out, d_lod);
+  });
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_raster_texture_mip_grad_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                           long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                           const void* d_tex, int tex_kind, int n_channels, int tex_height, int tex_width,
+                                           long long tex_frame_stride, int n_frames, double fx, double fy, double cx, double cy,
+                                           const float* d_mip, long long mip_frame_stride, int max_level, float lod_bias,
+                                           const float* d_grad_image, float* d_grad_uv, float* d_grad_tex, long long* d_workspace,
+                                           void* stream) {
+  const char* fn = "bodyfit_raster_texture_mip_grad_device";
+  bool work = false;
+  if (int rc = tx_check(fn, r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_kind, n_channels,
+                        tex_height, tex_width, tex_frame_stride, n_frames, &work))
+    return rc;
+  long long total = 0;
+  // (the pyramid is read for d_grad_uv only: without it d_mip may be NULL, as d_tex)
+  const TxMip M = txm_args(fx, fy, cx, cy, d_mip, tex_frame_stride, mip_frame_stride, tex_height, tex_width, max_level, lod_bias,
+                           &total);
+  if (int rc = txm_check(fn, fx, fy, cx, cy, lod_bias, d_grad_uv ? M.n_levels : 1, total, n_channels, d_mip, tex_frame_stride,
+                         mip_frame_stride))
+    return rc;
+  if (!work || (!d_grad_uv && !d_grad_tex)) return BODYFIT_OK;
+  if (!d_grad_image) return tx_invalid(fn, "d_grad_image is NULL");
+  if (d_grad_tex && !d_workspace) return tx_invalid(fn, "d_grad_tex without d_workspace");
+  const bodyfit::RasterView V = bodyfit::raster_view(r);
+  if (V.nF > 0 && d_grad_uv && !d_tex) return tx_invalid(fn, "d_grad_uv without d_tex");
+  HIP_TRY(hipSetDevice(V.device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+                           tex_frame_stride, n_frames);
+  int B = 0;      // the bit length of the pixel count: total < 2^B
+  while ((A.total >> B) != 0) ++B;
+  const long long n_textures = tex_frame_stride ? n_frames : 1;
+  const long long pyramid = (long long)tex_height * tex_width + total;       // texels of one pyramid, level 0 first
+  const long long n_tex = (long long)tex_height * tex_width * n_channels * n_textures;
+  const long long n_work = pyramid * n_channels * n_textures;
+  const long long n_grad = A.total * n_channels;
+  if (d_grad_tex && n_work >= (1ll << 39)) return tx_invalid(fn, "2^39 pyramid elements or more in one call");
+  HIP_TRY(hipMemsetAsync(V.d_scratch, 0, sizeof(unsigned), st));
+  if (d_grad_tex) HIP_TRY(hipMemsetAsync(d_workspace, 0, (size_t)n_work * sizeof(long long), st));
+  const unsigned mblocks = (unsigned)std::min<long long>((n_grad + 255) / 256, 4096);
+  BODYFIT_LAUNCH(k_tx_gmax, dim3(mblocks), dim3(256), 0, st, d_grad_image, n_grad, V.d_scratch);
+  const dim3 grid((unsigned)((A.total + 255) / 256));
+  unsigned long long* sums = d_grad_tex ? reinterpret_cast<unsigned long long*>(d_workspace) : nullptr;
+  tx_dispatch(tex_kind, n_channels, [&](auto c, auto* type) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(type)>>;
+    BODYFIT_LAUNCH((k_txm_grad<decltype(c)::value, T>), grid, dim3(256), 0, st, A, M, static_cast<const T*>(d_tex), d_grad_image,
+                   V.d_scratch, B, pyramid, d_grad_uv, sums);
+  });
+  if (d_grad_tex)
+    BODYFIT_LAUNCH(k_txm_fold, dim3((unsigned)((n_tex + 255) / 256)), dim3(256), 0, st, sums, M, n_channels, pyramid, n_tex,
+                   V.d_scratch, B, d_grad_tex);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

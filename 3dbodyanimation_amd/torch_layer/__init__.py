@@ -9,10 +9,12 @@ describes what it holds:
     depth        render_depth, visible_vertices, DepthMapTerm, depth_at_pixels, DepthResidualTerm
     silhouette   distance_transform, SilhouetteTerm, edge_weights, antialias, CoverageTerm
     appearance   render_attributes, sample_images, fuse_vertex_colours, PhotometricTerm, RenderedPhotometricTerm
-    texture      render_texture, TexturedPhotometricTerm, bake_texture
+    texture      render_texture, TexturedPhotometricTerm, bake_texture; with mipmaps (a trilinear lookup at the pixel's level of
+                 detail and its gradients): texture.render_texture_mip and TexturedPhotometricTerm.mipmaps()
     _common      what they share: point sets, the kept handles (one cache each), the argument checks, the row helpers
 
-Every public name is importable from here, and so are the private ones the tests and tools reach.
+Every public name of the recorded surface (tests/golden/torch_layer_surface.json) is importable from here, and so are the private
+ones the tests and tools reach; texture.render_texture_mip, added after that record, is imported from its module.
 """
 import torch  # noqa: F401  (callers reach torch through the layer)
 

@@ -9,12 +9,21 @@ perspective-correct weights, then a bilinear texel lookup); its backward is body
 in the texels, summed in 64-bit integers), the rows VJP on the atlas's own surface handle for uv, and for the vertices the rows of
 bodyfit_raster_interp_rows_indexed_device.  TexturedPhotometricTerm is appearance.RenderedPhotometricTerm with a texture in place
 of the vertex colours; bake_texture is the texture counterpart of fuse_vertex_colours.
+
+    image, face = render_texture_mip(verts, faces, intr, (H, W), uv, uv_faces, tex, interior=True, lod_bias=0.0)
+    term = TexturedPhotometricTerm(video, intr, faces, uv, uv_faces).mipmaps()
+
+are the same with MIPMAPS: the texture's pyramid (bodyfit_raster_texture_mip_build_device), then
+bodyfit_raster_texture_mip_device and bodyfit_raster_texture_mip_grad_device: a trilinear lookup at each pixel's level of detail,
+differentiated at that fixed level.  render_texture_mip is reached through this module (the package re-exports the names its
+recorded surface holds; render_texture and the term's constructor keep their signatures).  bake_texture stays level 0.
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
+from .. import api
 from ._common import (_check_background, _check_intr_size, _check_verts, _host_faces, _pixel_rows_vjp, _point_set, _stream,
                       _surface_handle)
 from .appearance import _PixelPhotometricTerm, _check_frames, _check_images, _interior_rows
@@ -49,9 +58,19 @@ def _check_texture(tex, F: int, device):
     return (0 if tex.dtype == torch.uint8 else 1), tex.ndim == 3
 
 
+def _check_mip(max_mip_level, lod_bias):
+    """(max_level for the ABI: -1 = as many as exist, lod_bias)"""
+    if max_mip_level is not None and int(max_mip_level) < 0:
+        raise ValueError("max_mip_level is None or >= 0")
+    if lod_bias != lod_bias:
+        raise ValueError("lod_bias is NaN")
+    return (-1 if max_mip_level is None else int(max_mip_level), float(lod_bias))
+
+
 class _RenderTexture(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tex, uv, verts, faces, intr, size, uv_faces, uv_faces_device, background, z_near, cull_backfaces, interior):
+    def forward(ctx, tex, uv, verts, faces, intr, size, uv_faces, uv_faces_device, background, z_near, cull_backfaces, interior,
+                mip=None):
         raster, depth, face, bary = _render(verts, faces, intr, size, z_near, cull_backfaces, True)
         v, vs, F, _ = _point_set("verts", verts.detach(), None)
         H, W = int(size[0]), int(size[1])
@@ -61,15 +80,28 @@ class _RenderTexture(torch.autograd.Function):
         image = torch.empty((F, H, W, C), dtype=torch.float32, device=v.device)
         weight = torch.empty((F, H, W, 3), dtype=torch.float32, device=v.device)
         look = (u.shape[0], kind, C, Ht, Wt, 0 if shared else Ht * Wt * C, F)
-        if F > 0:
+        pyramid = None          # mip: (max_level, lod_bias, the pyramid f32 [1 or F, total C], its stride), built once per call
+        if mip is not None:
+            total = api.texture_mip_layout(Ht, Wt, mip[0])[3]
+            pyramid = torch.empty((1 if shared else F, total * C), dtype=torch.float32, device=v.device)
+            mip = (mip[0], mip[1], pyramid, pyramid.shape[1])
+        if F > 0 and mip is None:
             with torch.cuda.device(v.device):
                 raster.texture_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, u.data_ptr(), look[0],
                                       uv_faces_device.data_ptr(), t.data_ptr(), kind, C, Ht, Wt, look[5], F, background,
                                       image.data_ptr(), weight.data_ptr(), None, _stream())
+        elif F > 0:
+            with torch.cuda.device(v.device):
+                raster.texture_mip_build_device(t.data_ptr(), kind, C, Ht, Wt, look[5], pyramid.shape[0], mip[0], pyramid.data_ptr(),
+                                                mip[3], _stream())
+                raster.texture_mip_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, u.data_ptr(), look[0],
+                                          uv_faces_device.data_ptr(), t.data_ptr(), kind, C, Ht, Wt, look[5], F, intr,
+                                          pyramid.data_ptr(), mip[3], mip[0], mip[1], background, image.data_ptr(),
+                                          weight.data_ptr(), None, None, _stream())
         want_tex = ctx.needs_input_grad[0] and kind == 1
         ctx.interior = bool(interior) and ctx.needs_input_grad[2]
         if want_tex or ctx.needs_input_grad[1] or ctx.interior:
-            ctx.look = (raster, vs, tuple(float(x) for x in intr), look, uv_faces, want_tex, faces)
+            ctx.look = (raster, vs, tuple(float(x) for x in intr), look, uv_faces, want_tex, faces, mip)
             ctx.save_for_backward(face, bary, weight, v, u, t, uv_faces_device)
         ctx.mark_non_differentiable(face, depth)
         return image, face, depth
@@ -78,21 +110,32 @@ class _RenderTexture(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_image, _g_face, _g_depth):
         if not hasattr(ctx, "look"):
-            return (None,) * 12
+            return (None,) * 13
         face, bary, weight, v, u, t, uv_faces_device = ctx.saved_tensors
-        raster, vs, intr, (T, kind, C, Ht, Wt, tex_stride, F), uv_faces, want_tex, faces = ctx.look
+        raster, vs, intr, (T, kind, C, Ht, Wt, tex_stride, F), uv_faces, want_tex, faces, mip = ctx.look
         dev, (H, W) = face.device, face.shape[1:]
         want_uv = ctx.needs_input_grad[1] or ctx.interior
         g_tex = torch.zeros(t.shape, dtype=torch.float32, device=dev) if want_tex else None
         g_uvpix = torch.zeros((F, H, W, 2), dtype=torch.float32, device=dev) if want_uv else None
         if g_image is not None and F * H * W > 0:
             gi = g_image.to(torch.float32).contiguous()
-            work = torch.empty(t.shape, dtype=torch.int64, device=dev) if want_tex else None
-            with torch.cuda.device(dev):
-                raster.texture_grad_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, u.data_ptr(), T,
-                                           uv_faces_device.data_ptr(), t.data_ptr(), kind, C, Ht, Wt, tex_stride, F, gi.data_ptr(),
-                                           g_uvpix.data_ptr() if want_uv else None, g_tex.data_ptr() if want_tex else None,
-                                           work.data_ptr() if want_tex else None, _stream())
+            outs = (g_uvpix.data_ptr() if want_uv else None, g_tex.data_ptr() if want_tex else None)
+            if mip is None:
+                work = torch.empty(t.shape, dtype=torch.int64, device=dev) if want_tex else None
+                with torch.cuda.device(dev):
+                    raster.texture_grad_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, u.data_ptr(), T,
+                                               uv_faces_device.data_ptr(), t.data_ptr(), kind, C, Ht, Wt, tex_stride, F,
+                                               gi.data_ptr(), *outs, work.data_ptr() if want_tex else None, _stream())
+            else:
+                max_level, lod_bias, pyramid, mip_stride = mip
+                # the int64 pyramid, level 0 first: Ht Wt C + the packed levels, per texture
+                work = (torch.empty((pyramid.shape[0], Ht * Wt * C + mip_stride), dtype=torch.int64, device=dev) if want_tex
+                        else None)
+                with torch.cuda.device(dev):
+                    raster.texture_mip_grad_device(face.data_ptr(), bary.data_ptr(), v.data_ptr(), vs.frame_stride, u.data_ptr(), T,
+                                                   uv_faces_device.data_ptr(), t.data_ptr(), kind, C, Ht, Wt, tex_stride, F, intr,
+                                                   pyramid.data_ptr(), mip_stride, max_level, lod_bias, gi.data_ptr(), *outs,
+                                                   work.data_ptr() if want_tex else None, _stream())
         g_uv = None
         if ctx.needs_input_grad[1]:
             # the pixels as rows of the ATLAS's own surface handle (T rows, uv_faces): g_uv[uv_faces[t][a]] += w_a (g_u, g_v, 0)
@@ -107,7 +150,7 @@ class _RenderTexture(torch.autograd.Function):
             surface = _surface_handle(dev.index, v.shape[1], faces)
             g_verts = _interior_rows(raster, surface, v, vs, intr, face, weight, u, 0, 2, g_uvpix if g_image is not None else None,
                                      attr_faces=uv_faces_device, n_attr_rows=T)
-        return (g_tex, g_uv, g_verts) + (None,) * 9
+        return (g_tex, g_uv, g_verts) + (None,) * 10
 
 
 def render_texture(verts: torch.Tensor, faces, intr, size, uv: torch.Tensor, uv_faces, tex: torch.Tensor, background=0.0,
@@ -130,8 +173,12 @@ def render_texture(verts: torch.Tensor, faces, intr, size, uv: torch.Tensor, uv_
           bodyfit_raster_interp_rows_indexed_device with attr = uv and the upstream gradient (g_u, g_v), summed by one
           bodyfit_surface_rows_vjp_device call (one host synchronisation lists the shaded pixels, as render_attributes').
     NOT part of it: visibility and coverage (antialias(image, verts, ...) adds the gradient through coverage), z_near and
-    culling.  NOT built: mipmaps or any minification filter: a body smaller on the screen than its atlas aliases, and the texels
-    no pixel's cell touches get no gradient."""
+    culling.  This lookup has NO minification filter: a body smaller on the screen than its atlas ALIASES, and the texels no
+    pixel's cell touches get no gradient; render_texture_mip (this module) is the lookup with mipmaps."""
+    return _render_texture(verts, faces, intr, size, uv, uv_faces, tex, background, z_near, cull_backfaces, interior, None)
+
+
+def _render_texture(verts, faces, intr, size, uv, uv_faces, tex, background, z_near, cull_backfaces, interior, mip):
     _check_verts(verts)
     _check_intr_size(intr, size)
     n_faces = _host_faces(faces).shape[0]
@@ -139,8 +186,30 @@ def render_texture(verts: torch.Tensor, faces, intr, size, uv: torch.Tensor, uv_
     _check_texture(tex, verts.shape[0], verts.device)
     bg = _check_background(background, tex.shape[-1])
     image, face, _ = _RenderTexture.apply(tex, uv, verts, faces, intr, size, uvf, uvf_device, bg, float(z_near), bool(cull_backfaces),
-                                          bool(interior))
+                                          bool(interior), mip)
     return image, face
+
+
+def render_texture_mip(verts: torch.Tensor, faces, intr, size, uv: torch.Tensor, uv_faces, tex: torch.Tensor, background=0.0,
+                       z_near: float = 0.1, cull_backfaces: bool = False, interior: bool = False,
+                       max_mip_level: int | None = None, lod_bias: float = 0.0):
+    """render_texture with MIPMAPS: the same arguments, the same outputs and the same three gradients, through the texture's
+    pyramid.  (A function of its own in this module, torch_layer.texture.render_texture_mip: render_texture keeps the signature
+    the package's recorded surface holds, and is the plain lookup bit for bit.)
+
+    The pyramid is built once per call (bodyfit_raster_texture_mip_build_device: levels by exact halving while the sizes stay
+    even, at most max_mip_level above level 0; None: as many as exist) and looked up trilinearly
+    (bodyfit_raster_texture_mip_device) at the level of detail of each pixel's footprint, L = log2(rho) + lod_bias clamped to the
+    pyramid, rho the larger singular value of the face's screen-to-texel map at the pixel.  The gradients
+    (bodyfit_raster_texture_mip_grad_device) are taken at the FIXED face image, pixel rays AND LEVEL OF DETAIL: tex (float32 only)
+    gets every texel under a pixel's footprint, in the level-0 layout, the exact adjoint of "average without rounding, then filter",
+    summed in 64-bit integers and bit-identical from run to run and under any permutation of the frames; uv and (interior=True)
+    verts go through render_texture's rows with the blended pixel gradients.  Where L = 0 (a one-level texture, lod_bias = -inf)
+    everything equals render_texture's bit for bit.
+    NOT built: the gradient through the level of detail, anisotropic filtering, wrap and mirror addressing, caller-supplied
+    pyramids, a mip-aware bake_texture."""
+    return _render_texture(verts, faces, intr, size, uv, uv_faces, tex, background, z_near, cull_backfaces, interior,
+                           _check_mip(max_mip_level, lod_bias))
 
 
 class TexturedPhotometricTerm(_PixelPhotometricTerm):
@@ -153,16 +222,26 @@ class TexturedPhotometricTerm(_PixelPhotometricTerm):
       sum over the pixels p of mask of rho(sum_c (R_c(p) - I_c(p))^2),    rho(s) = min(s, trunc^2) (trunc None: rho(s) = s).
     Differentiable in tex (every covered pixel writes into the four texels of its cell) and in verts: through the uv
     interpolation inside the faces and, with antialias, through coverage at the silhouettes.  One render per evaluation.  No
-    normal equations are built for it.  evaluate(verts, tex) returns the cost with its parts."""
+    normal equations are built for it.  evaluate(verts, tex) returns the cost with its parts.  term.mipmaps(...) switches the
+    render to render_texture_mip's: a body smaller on the screen than its atlas is then minified through the texture's pyramid,
+    and every texel under a pixel's footprint gets a gradient."""
 
     _VIDEO_NAME, _VIDEO_FRAMES = "the video", "the video has"
 
     def __init__(self, video: torch.Tensor, intr, faces, uv: torch.Tensor, uv_faces, trunc: float | None = None, background=0.0,
                  mask: torch.Tensor | None = None, antialias: bool = True, z_near: float = 0.1, cull_backfaces: bool = False):
         super().__init__(video, intr, faces, trunc, background, mask, antialias, z_near, cull_backfaces)
+        self.mip = None
         self.uv_faces, uvf_device = _check_atlas(uv, uv_faces, self.faces.shape[0], self.images.device)
         self.register_buffer("uv", uv.detach().contiguous())
         self.register_buffer("uv_faces_device", uvf_device)
+
+    def mipmaps(self, enable: bool = True, max_mip_level: int | None = None, lod_bias: float = 0.0):
+        """Render through the texture's pyramid from now on (render_texture_mip's max_mip_level and lod_bias), or with
+        enable=False through the plain lookup again, which is what a new term does.  Returns the term:
+        term = TexturedPhotometricTerm(...).mipmaps()."""
+        self.mip = _check_mip(max_mip_level, lod_bias) if enable else None
+        return self
 
     def evaluate(self, verts: torch.Tensor, tex: torch.Tensor) -> dict:
         """term(verts, tex) with what it was built from: cost (f64, with the gradient), image f32 [F, H, W, C] (what was compared
@@ -173,7 +252,8 @@ class TexturedPhotometricTerm(_PixelPhotometricTerm):
         if tex.shape[-1] != self.images.shape[3]:
             raise ValueError(f"tex has {tex.shape[-1]} channels, the video {self.images.shape[3]}")
         image, face, depth = _RenderTexture.apply(tex, self.uv, verts, self.faces, self.intr, self.size, self.uv_faces,
-                                                  self.uv_faces_device, self.background, self.z_near, self.cull_backfaces, True)
+                                                  self.uv_faces_device, self.background, self.z_near, self.cull_backfaces, True,
+                                                  self.mip)
         return self._against_video(verts, image, face, depth)
 
     def forward(self, verts: torch.Tensor, tex: torch.Tensor) -> torch.Tensor:

@@ -1287,9 +1287,9 @@ int bodyfit_raster_sample_device(bodyfit_raster* r, const float* d_points, long 
  * outside {0, 1}, Ht or Wt outside 1 .. 16384, a non-zero texture stride below Ht Wt n_channels, and with frames to write: NULL
  * d_face / d_bary / d_image, NULL d_verts / d_uv_faces / d_tex (n_faces > 0), NULL d_uv (n_faces > 0 and n_uv > 0), a vertex stride
  * below 3 n_verts, 2^39 pixels or more.
- * NOT BUILT: mipmaps or any minification filter, the screen-space uv derivatives they need, wrap and mirror addressing.  A body that
- * is smaller on the screen than its atlas ALIASES (a pixel reads one 2 x 2 cell, whatever area of the atlas it covers), and the
- * texels no pixel's cell touches receive no gradient.                                                                          */
+ * NOT BUILT HERE: wrap and mirror addressing.  THIS entry has no minification filter: a body that is smaller on the screen than its
+ * atlas ALIASES (a pixel reads one 2 x 2 cell, whatever area of the atlas it covers), and the texels no pixel's cell touches receive
+ * no gradient.  bodyfit_raster_texture_mip_device (MIPMAPS OF THE TEXTURE LOOKUP, below) is the lookup with mipmaps.            */
 int bodyfit_raster_texture_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
                                   long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
                                   const void* d_tex, int tex_kind, int n_channels, int tex_height, int tex_width,
@@ -1356,6 +1356,131 @@ int bodyfit_raster_texture_grad_device(bodyfit_raster* r, const int32_t* d_face,
                                        const float* d_grad_image, float* d_grad_uv /* may be NULL */,
                                        float* d_grad_tex /* may be NULL */, long long* d_workspace /* may be NULL without d_grad_tex */,
                                        void* stream);
+/* MIPMAPS OF THE TEXTURE LOOKUP (k_txm_build, k_txm_forward, k_txm_grad, k_txm_fold, k_texture.hip): the minification filter of
+ * Laine et al. (2020): a pyramid of the texture, a level of detail per pixel from the face's footprint, and a trilinear lookup.
+ * The entries above are unchanged; these stand next to them.
+ * THE PYRAMID.  Level 0 is the texture.  Level l + 1 exists iff l < max_level (max_level < 0: as many as exist), (H_l, W_l) != (1, 1)
+ * and each of H_l, W_l is EVEN OR 1; a dimension > 1 is halved, a dimension of 1 stays 1.  There are no odd halvings: a texel of level
+ * l + 1 is exactly the union of its children in uv, so the texel-centre convention above holds on every level with (W_l, H_l) for
+ * (Wt, Ht).  7 x 5 has one level, 12 x 20 three (12 x 20, 6 x 10, 3 x 5), 1 x 8 four, 64 x 64 seven, 16384 x 16384 fifteen =
+ * BODYFIT_TX_MAX_LEVELS.  bodyfit_texture_mip_layout (host only, no GPU): *n_levels, heights[l] = H_l, widths[l] = W_l and offsets[l],
+ * the TEXEL offset of level l in a packed buffer that holds levels 1 .. n_levels - 1 (offsets[0] = 0 is not used), for l < n_levels
+ * (each array BODYFIT_TX_MAX_LEVELS long, or NULL), and *total, that buffer's texels.  BODYFIT_ERR_INVALID: a size outside 1 ..
+ * 16384, NULL n_levels.
+ * bodyfit_raster_texture_mip_build_device writes d_mip f32: per texture the levels 1 .. n_levels - 1, level l at offsets[l] n_channels,
+ * [H_l][W_l][n_channels] interleaved; textures mip_frame_stride ELEMENTS apart (>= total n_channels; not used with n_textures = 1).
+ * Level l + 1 is built from the STORED level l (d_tex in its own type for l = 0, the f32 level otherwise):
+ *   ((t00 + t01) + (t10 + t11)) * 0.25   over the children (2i, 2j), (2i, 2j + 1), (2i + 1, 2j), (2i + 1, 2j + 1), in f64, rounded once to
+ * f32;  (t0 + t1) * 0.5 over the two children where one dimension is 1.  One thread per output element, plain stores, one launch per
+ * level: bit-identical from run to run.  Asynchronous on `stream`, no host synchronisation.  n_textures == 0 or one level: a no-op.
+ * BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_textures, n_channels, tex_kind or a size out of range, with
+ * n_textures > 1 a texture stride below Ht Wt n_channels or (more than one level) a pyramid stride below total n_channels, and with
+ * levels to write NULL d_tex or d_mip, 2^39 elements or more.
+ * THE LOOKUP WITH A LEVEL OF DETAIL, bodyfit_raster_texture_mip_device: the arguments of bodyfit_raster_texture_device, the render's
+ * fx, fy, cx, cy, the pyramid (d_mip, mip_frame_stride; with tex_frame_stride == 0 ONE pyramid serves every frame and the stride is
+ * not used), max_level (the one the pyramid was built with), lod_bias, and unless NULL d_lod f32 [n_frames][H][W]: the L that was
+ * used, 0 on void pixels.  The void rule, the weights w_a, uv and the clamp are the plain lookup's (the same device function):
+ * d_weight and d_uv_out are its bits.  All of d_verts' coordinates are read here.
+ * FOOTPRINT, analytically from the face (no differences of neighbouring pixels).  p_a = (fx X_a / Z_a + cx, fy Y_a / Z_a + cy), A =
+ * (p1 - p0) x (p2 - p0) the render's doubled area, grad lambda_a = (p_b,y - p_c,y, p_c,x - p_b,x) / A (b, c the corners after a); with
+ * q_a = lambda_a / Z_a of the stored barycentrics and S = sum q_a:  d(uv)/ds = sum_a (grad lambda_a / Z_a)(uv_a - uv) / S, a 2 x 2
+ * matrix; J = diag(Wt, Ht) d(uv)/ds in level-0 texels per pixel; rho^2 the largest eigenvalue of J J^T (rotation-invariant),
+ *   rho^2 = (a + b) / 2 + sqrt(((a - b) / 2)^2 + c^2),   a, b the squared norms of J's columns, c their dot product;
+ *   L = clamp(log2(rho^2) / 2 + lod_bias, 0, n_levels - 1).
+ * L = 0 where rho^2 is NaN or +inf, where A = 0 or is not finite, or where an X or Y of the face is not finite (the plain rule only
+ * looks at Z; hand-made face images reach such faces); rho^2 = 0 gives -inf and clamps to 0; lod_bias may be -inf or +inf.
+ * Order (f64, unfused): p_a as the render's; A as the render's; h_a = ((p_b,y - p_c,y) / A) / Z_a and ((p_c,x - p_b,x) / A) / Z_a;
+ * d_a = uv_a - uv^; ((h_0 d_0 + h_1 d_1) + h_2 d_2) / S; the product with Wt or Ht; a = J00 J00 + J10 J10, b, c alike; hs = 0.5 (a +
+ * b), hd = 0.5 (a - b); rho^2 = hs + sqrt(hd hd + c c); 0.5 log2(rho^2) + lod_bias; the clamp; THE ROUNDING TO f32: the f32 in d_lod
+ * IS the L that the filter and the gradients use, so everything below that is stated "at the returned L^" can be checked from d_lod.
+ * FILTER.  l0 = floor(L), f = L - l0 (exact).  P_l is the clamp-to-edge bilinear patch of level l at the pixel's uv, each level with
+ * its OWN clamp and cell (x_l = u W_l - 1/2, ...; the same helpers).  image_c = (1 - f) P_l0 + f P_(l0+1): 1 - f, two products and a
+ * sum in f64, rounded once.  WHERE f = 0 ONLY LEVEL l0 IS READ and image_c = P_l0 with no blend arithmetic: with a lod_bias that
+ * forces L = 0 everywhere (-inf, -1000), or with a one-level texture, d_image is BIT-IDENTICAL to bodyfit_raster_texture_device's,
+ * and a NaN in a level that is not used cannot leak in.
+ * CONTRACT.  With the plain lookup's u, U, P_x, kappa (of level 0: the largest of the levels'), the render's P_t, Q_t, R_t of the face,
+ * Lambda = the sum of the pixel's three stored barycentrics, eps = 2^-53 and
+ *   D = 12 U R_t Q_t / (P_t Lambda)              (no entry of d(uv)/ds exceeds it),
+ *   E_J = k_J eps P_x D (1 + 4 Q_t), k_J = 64     (the computed rho^ is within E_J of rho),
+ *   d_log = k_L eps (1 + |log2(rho^2) / 2| + |lod_bias|), k_L = 24,
+ * the returned L^ is the f32 rounding (u L) of a value in [clamp(log2(max(rho - E_J, 0)) + lod_bias - d_log), clamp(log2(rho + E_J) +
+ * lod_bias + d_log)]; delta_L is the larger distance of that interval's ends from the exact L, plus u L.  It holds for 80 eps Q_t <= 1/2;
+ * a face beyond that (a sliver whose area is lost in P_t^2) has delta_L = n_levels - 1: nothing is said about its level.  With
+ * I(L) = (1 - f) B_l0 + f B_(l0+1) over the STORED pyramid, B_l the continuous surface of level l, and M the largest |texel| among the
+ * exact and the returned cells of every level from floor(L - delta_L) to ceil(L + delta_L):
+ *   |image^_c - I_c(L)| <= u |I_c| + kappa M + 2 M delta_L,     and at the returned level   |image^_c - I_c(L^)| <= u |I_c| + kappa M.
+ * Derivation.  A coordinate of p_a: 3 eps P_t; a difference of two: 8 eps P_t against |.| <= 2 P_t; A: 80 eps P_t^2 (the render's
+ * derivation), relative 80 eps Q_t.  (p_b,y - p_c,y) / A: at most g = 2 P_t / |A| = 2 Q_t / P_t, off by g eps (5 + 80 Q_t) to first
+ * order; / Z_a: one more, at most g / Z_min.  d_a: uv^ is within 8 eps U of uv (the plain derivation), the difference rounds: 10 eps U
+ * against |d_a| <= 2 U.  A product h_a d_a <= T = 2 U g / Z_min, off by T eps (13 + 80 Q_t); the sum of three: 3 T eps (15 + 80 Q_t).
+ * S >= Lambda / Z_max, computed within 3 eps; the quotient: entries <= 3 T Z_max / Lambda = D, off by D eps (19 + 80 Q_t); the product
+ * with Wt or Ht: P_x D eps (20 + 80 Q_t).  The largest singular value moves by at most the Frobenius norm of the change of J, 2 entries
+ * a side: |rho^ - rho| <= 2 P_x D eps (20 + 80 Q_t) = 40 eps P_x D (1 + 4 Q_t), stated as k_J = 64 for the terms of second order.
+ * a, b, c, hs, hd and the sum under the root carry at most 12 eps (a + b) <= 24 eps rho^2 into rho^2; sqrt is correctly rounded and
+ * log2 is within 1 ulp on the device (the ROCm device library's documented accuracy for f64): 18 eps + 2 eps |log2(rho^2) / 2|, the sum
+ * with lod_bias one more: inside d_log.  The filter is CONTINUOUS in L (at f -> 1 it is P_(l0+1), which is the next interval's f = 0)
+ * with slope P_(l0+1) - P_l0, at most 2 M: a wrong floor next to an integer L costs 2 M delta_L like any other error in L.  Each patch
+ * is within kappa_l M of its surface before the store (the plain derivation, 9 of the 16 units), the blend adds 3 eps M.
+ * THE GRADIENTS, bodyfit_raster_texture_mip_grad_device (k_tx_gmax, k_txm_grad, k_txm_fold), at the FIXED face image, pixel rays and
+ * LEVEL OF DETAIL: L and f are constants; the gradient through rho is NOT built.
+ * (a) d_grad_uv = (1 - f) [level l0's patch derivative times (W_l0, H_l0)] + f [level l0 + 1's, likewise], each level with its own
+ *     clamp-active rule, the plain order inside a level, then 1 - f, two products and a sum; where f = 0 the single-level form, which
+ *     for l0 = 0 is the plain entry's bit for bit.  Contract at the returned L^: the plain (a) per level, blended with (1 - f, f), plus
+ *     the store's u |g|; against the exact L add 4 M P_x delta_L sum_c |G_c| (the blend is continuous in L, a level's g is at most
+ *     2 M P_x sum_c |G_c|).
+ * (b) d_grad_tex in the LEVEL-0 texture's layout (shared: summed over all frames): the exact adjoint of "build the pyramid by
+ *     UNROUNDED averaging, then filter".  A pixel contributes fl(G_c fl((1 - f) omega_k)) to its 4 texels of level l0 and, where f !=
+ *     0, fl(G_c fl(f omega'_k)) to its 4 texels of level l0 + 1 (f = 0: fl(G_c omega_k), the plain contribution); each is scaled by 2^s,
+ *     rounded to int64 and added with a no-return 64-bit INTEGER atomic into d_workspace, int64 with the pyramid's packed layout and
+ *     LEVEL 0 FIRST: (Ht Wt + total) n_channels elements per texture, level l >= 1 at (Ht Wt + offsets[l]) n_channels; the entry zeroes
+ *     it.  s = 60 - B - E holds as it is: PER LEVEL a texel still receives at most 4 N contributions (a pixel gives a level at most 4),
+ *     each |G_c share omega_k| <= Gmax < 2^E since 0 <= (1 - f), f, omega_k <= 1: every partial sum stays under 2^62.  Gmax = 0, NaN and
+ *     infinity are handled as in the plain entry (k_tx_gmax is the same kernel).
+ *     FOLD, one thread per level-0 texel element (i, j, c): in f64 and in the fixed order l = 0, 1, ..., n_levels - 1,
+ *       acc = (double)S_0[i][j][c] 2^-s;   acc = acc + ((double)S_l[i_l][j_l][c] 2^-s) a_l,
+ *     (i_l, j_l) the texel's ancestor on level l (a halved dimension shifts right by one per level) and a_l the exact power of two that
+ *     is the product of the build's 1/4 and 1/2 factors; the float of acc is stored.  The scatter is bit-identical by integer
+ *     associativity, the fold is a fixed-order gather: d_grad_tex is bit-identical from run to run and for any permutation of the
+ *     frames.  With one level, or L = 0 everywhere, it is the plain entry's bit for bit.
+ *     Contract, with m_l and A_l the plain (b)'s m and A of the texel's ancestor on level l, against g* = sum_l a_l S*_l (S*_l the exact
+ *     sums at the returned cells, weights and L^), k_m = 24:
+ *       |g^ - g*| <= u |g*| + sum_l a_l m_l 2^-(s + 1) + k_m eps sum_l a_l A_l.
+ *     Derivation: omega^ within 3 eps, 1 - f one, the share's product one, the product with G_c one: 6 eps A_l; (double)S_l one; the
+ *     n_levels - 1 <= 14 sums of the fold one each on partial sums <= sum_l a_l A_l: together below 22 eps, stated as 24.
+ * RUN COMBINING (BODYFIT_TXM_COMBINE) is the plain entry's with the key (level, cell) of both of a lane's levels; the bits are the
+ * same either way.  Both forms were measured on a magnified and on a minified render ("Mipmaps"): combining is
+ * the faster on both and is the default (1).  The per-lane integers and addresses are indexed with compile-time constants only (the
+ * one or two levels are unrolled): the kernels use no scratch memory.
+ * The vertex gradient is the plain path's: d_grad_uv through bodyfit_raster_interp_rows_indexed_device and the rows VJP.
+ * Asynchronous on `stream`, no host synchronisation; the Gmax word is shared as in the plain entry.  BODYFIT_ERR_INVALID (nothing is
+ * launched): every case of the plain entries, and fx or fy <= 0 or a non-finite intrinsic, a NaN lod_bias, NULL d_mip with more than
+ * one level (the gradient entry: only with d_grad_uv), with per-frame textures a pyramid stride below total n_channels, 2^39
+ * workspace elements or more.
+ * NOT BUILT: the gradient through the level of detail, anisotropic filtering, wrap and mirror addressing, caller-supplied pyramids
+ * (the lookup reads what the build entry's layout says), a mip-aware bake (torch_layer.bake_texture stays level 0), the term's
+ * normal equations, the C++ mirror header's entries.                                                                            */
+#define BODYFIT_TX_MAX_LEVELS 15
+int bodyfit_texture_mip_layout(int tex_height, int tex_width, int max_level, int* n_levels, int* heights /* may be NULL */,
+                               int* widths /* may be NULL */, long long* offsets /* may be NULL */, long long* total /* may be NULL */);
+int bodyfit_raster_texture_mip_build_device(bodyfit_raster* r, const void* d_tex, int tex_kind, int n_channels, int tex_height,
+                                            int tex_width, long long tex_frame_stride, int n_textures, int max_level, float* d_mip,
+                                            long long mip_frame_stride, void* stream);
+int bodyfit_raster_texture_mip_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                      long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                      const void* d_tex, int tex_kind, int n_channels, int tex_height, int tex_width,
+                                      long long tex_frame_stride, int n_frames, double fx, double fy, double cx, double cy,
+                                      const float* d_mip /* may be NULL with one level */, long long mip_frame_stride, int max_level,
+                                      float lod_bias, const float* background /* host [4]; may be NULL */, float* d_image,
+                                      float* d_weight /* may be NULL */, float* d_uv_out /* may be NULL */,
+                                      float* d_lod /* may be NULL */, void* stream);
+int bodyfit_raster_texture_mip_grad_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                           long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces,
+                                           const void* d_tex /* may be NULL without d_grad_uv */, int tex_kind, int n_channels,
+                                           int tex_height, int tex_width, long long tex_frame_stride, int n_frames, double fx,
+                                           double fy, double cx, double cy, const float* d_mip /* may be NULL without d_grad_uv */,
+                                           long long mip_frame_stride, int max_level, float lod_bias, const float* d_grad_image,
+                                           float* d_grad_uv /* may be NULL */, float* d_grad_tex /* may be NULL */,
+                                           long long* d_workspace /* may be NULL without d_grad_tex */, void* stream);
 /* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster.hip): the coverage of a render as a smooth
  * function of the vertices, after Laine et al., "Modular Primitives for High-Performance Differentiable Rendering" (2020).  Only
  * COVERAGE carries a gradient here: how an attribute interpolates inside a face as its corners move is not part of it.
