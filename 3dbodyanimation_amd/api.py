@@ -327,6 +327,16 @@ def load_library():
                                                            C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                                            C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                                            C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_raster_light_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_light_grad_layout.argtypes = [C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_longlong)]
+    lib.bodyfit_raster_light_grad_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                     C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_surface_vertex_normals_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
+                                                              C.c_longlong, C.c_void_p]
     _lib = lib
     return lib
 
@@ -358,6 +368,15 @@ def texture_mip_layout(tex_height: int, tex_width: int, max_level: int = -1):
                                                      C.byref(total)))
     k = n.value
     return k, [(hs[l], ws[l]) for l in range(k)], [off[l] for l in range(k)], total.value
+
+
+def light_grad_layout(pixels_per_frame: int, n_channels: int, n_frames: int):
+    """bodyfit_light_grad_layout (host only): (the pixels of a chunk of light_grad_device's reduction, the chunks per frame, the
+    f64 elements of its workspace)"""
+    chunk, n, work = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    _check(load_library().bodyfit_light_grad_layout(int(pixels_per_frame), int(n_channels), int(n_frames), C.byref(chunk),
+                                                    C.byref(n), C.byref(work)))
+    return chunk.value, n.value, work.value
 
 
 def _c64(a):
@@ -954,6 +973,15 @@ class Surface:
         _check(load_library().bodyfit_surface_vertex_normals_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
                                                                     d_normals_ptr, stream))
 
+    def vertex_normals_vjp_device(self, d_verts_ptr: int, verts_frame_stride: int, n_frames: int, d_grad_normals_ptr: int,
+                                  d_grad_verts_ptr: int, grad_frame_stride: int, stream: int | None = None):
+        """bodyfit_surface_vertex_normals_vjp_device: for grad_normals [F, n_verts, 3] f32 (dense) the gradient in the vertices
+        through vertex_normals_device, [n_verts, 3] f32 per frame and grad_frame_stride floats apart: the exact adjoint at the
+        f32 vertices, gathered in f64 in a fixed order (no atomics), 0 through a vertex whose normal the forward wrote as 0."""
+        _check(load_library().bodyfit_surface_vertex_normals_vjp_device(self.h, d_verts_ptr, int(verts_frame_stride), int(n_frames),
+                                                                        d_grad_normals_ptr, d_grad_verts_ptr,
+                                                                        int(grad_frame_stride), stream))
+
     def laplacian_device(self, d_field_ptr: int, field_stride: int, n_fields: int, d_out_ptr: int, transpose: bool = False,
                          stream: int | None = None):
         """bodyfit_surface_laplacian_device: the uniform mesh Laplacian l_i = x_i - mean over i's faces of the other two corners
@@ -1215,6 +1243,35 @@ class Raster:
             int(tex_kind), int(n_channels), int(tex_height), int(tex_width), int(tex_frame_stride), int(n_frames), float(intr[0]),
             float(intr[1]), float(intr[2]), float(intr[3]), d_mip_ptr, int(mip_frame_stride), int(max_level), float(lod_bias),
             d_grad_image_ptr, d_grad_uv_ptr, d_grad_tex_ptr, d_workspace_ptr, stream))
+
+    def light_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                     d_normals_ptr: int | None, normals_frame_stride: int, d_albedo_ptr: int, n_channels: int, d_light_ptr: int,
+                     light_frame_stride: int, n_frames: int, d_image_ptr: int, d_normal_ptr: int | None = None,
+                     d_shading_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_raster_light_device: image [F, H, W, n_channels] f32 = albedo x s(n), s_c = sum_k light[k][c] b_k(n) with
+        the nine second-order polynomials b of the unit normal n interpolated from the per-vertex normals [F, n_verts, 3] f32
+        with the shade's weights; light f32 [9, n_channels], light_frame_stride floats between frames (0: shared).  An unlit
+        pixel (void, a non-finite or cancelling normal) passes its albedo through.  Unless None, normal [F, H, W, 3] f32 and
+        shading [F, H, W, n_channels] f32.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_light_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_normals_ptr, int(normals_frame_stride),
+            d_albedo_ptr, int(n_channels), d_light_ptr, int(light_frame_stride), int(n_frames), d_image_ptr, d_normal_ptr,
+            d_shading_ptr, stream))
+
+    def light_grad_device(self, d_face_ptr: int, d_bary_ptr: int, d_verts_ptr: int | None, verts_frame_stride: int,
+                          d_normals_ptr: int | None, normals_frame_stride: int, d_albedo_ptr: int, n_channels: int,
+                          d_light_ptr: int, light_frame_stride: int, n_frames: int, d_grad_image_ptr: int,
+                          d_grad_albedo_ptr: int | None, d_grad_m_ptr: int | None, d_grad_light_ptr: int | None,
+                          d_workspace_ptr: int | None, stream: int | None = None):
+        """bodyfit_raster_light_grad_device: for grad_image [F, H, W, n_channels] f32 the gradients of light_device's image
+        in the albedo [F, H, W, n_channels], in the unnormalised interpolated normal [F, H, W, 3] (what the rows VJP takes) and
+        in the light, ALWAYS per frame [F, 9, n_channels]; each may be None.  The light's is reduced in f64 in a fixed order
+        through the f64 workspace of light_grad_layout(...)[2] elements: no atomics, bit-identical from run to run and
+        whatever the batch around a frame.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_raster_light_grad_device(
+            self.h, d_face_ptr, d_bary_ptr, d_verts_ptr, int(verts_frame_stride), d_normals_ptr, int(normals_frame_stride),
+            d_albedo_ptr, int(n_channels), d_light_ptr, int(light_frame_stride), int(n_frames), d_grad_image_ptr,
+            d_grad_albedo_ptr, d_grad_m_ptr, d_grad_light_ptr, d_workspace_ptr, stream))
 
     def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_frame_stride: int, n_frames: int, invert: bool,
                         d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):

@@ -11,6 +11,7 @@ describes what it holds:
     appearance   render_attributes, sample_images, fuse_vertex_colours, PhotometricTerm, RenderedPhotometricTerm
     texture      render_texture, TexturedPhotometricTerm, bake_texture; with mipmaps (a trilinear lookup at the pixel's level of
                  detail and its gradients): texture.render_texture_mip and TexturedPhotometricTerm.mipmaps()
+    lighting     lighting.vertex_normals (differentiable), sh_basis, shade, LitPhotometricTerm (names reached through the module)
     _common      what they share: point sets, the kept handles (one cache each), the argument checks, the row helpers
 
 Every public name of the recorded surface (tests/golden/torch_layer_surface.json) is importable from here, and so are the private

@@ -662,6 +662,32 @@ int bodyfit_surface_winding_device(bodyfit_surface* s, const bodyfit_pointset* q
  * BODYFIT_ERR_INVALID: NULL handle / d_verts / d_normals, a negative n_frames, a stride below 3 n_verts.                      */
 int bodyfit_surface_vertex_normals_device(bodyfit_surface* s, const float* d_verts, long long verts_frame_stride, int n_frames,
                                           float* d_normals, void* stream);
+/* THE VERTEX NORMALS' ADJOINT (k_vn_h, k_vn_vjp, k_light.hip): for an upstream d_grad_normals f32 [F][n_verts][3] = dL/dn, dense,
+ * d_grad_verts f32 [n_verts][3] per frame, grad_frame_stride floats between frames (>= 3 n_verts; its own stride) = dL/dverts through
+ * bodyfit_surface_vertex_normals_device at the f32 vertices; every element of the [n_verts][3] blocks is written.
+ * DEFINITION.  s_i = sum_{t holds i} N_t, N_t = (v1 - v0) x (v2 - v0), n_i = s_i / |s_i|;
+ *   h_i = (g_i - n_i (n_i . g_i)) / |s_i|, and h_i = 0 where the forward wrote 0 (no face, a zero sum, a non-finite corner);
+ *   a_t = (h_i0 + h_i1) + h_i2;       dL/dv_{t,a} += (v_{t,a+1} - v_{t,a+2}) x a_t, corner indices cyclic.
+ * A face that repeats a vertex id contributes nothing (its N_t is identically 0), and neither does a face whose a_t is exactly 0 (so
+ * a non-finite vertex, whose faces all have h = 0 at their corners, spreads nothing and receives 0).  The upstream is plain IEEE.
+ * Two passes.  The first, one thread per (frame, vertex), forms s_i by the FORWARD's arithmetic (the same faces in the same order by
+ * the same f64 operations: n_i is the forward's before its store) and stores h_i as f64 in the handle's workspace.  The second,
+ * one thread per (frame, vertex), gathers over the vertex's entries of the handle's vertex -> corner table in ascending order in
+ * f64 (the edge, a difference of f32 corners, is exact; products and sums unfused) and rounds ONCE.  No atomics, frame-independent,
+ * bit-identical from run to run.
+ * CONTRACT, with u = 2^-24, eps = 2^-53, k_v = 128, c_i of the forward, and per face A_t = sum over its corners a of c_ia |g_ia| /
+ * |s_ia| (>= |a_t|):       |gv^ - gv*| <= u |gv*| + k_v eps sum over the vertex's faces of |v_{t,a+1} - v_{t,a+2}| A_t   per component.
+ * Derivation.  The forward's contract puts n_i within 8 eps c_i of exact and |s_i| within 8 eps c_i relative; h_i: a dot product
+ * (5 eps), a product, a difference, a quotient: |dh_i| <= (2 x 8 c_i + 8 c_i + 6) eps |g_i| / |s_i| <= 32 c_i eps |g_i| / |s_i|.
+ * a_t: the three dh and two sums: 34 eps A_t.  A component of the cross product: two products and a difference of magnitudes <=
+ * |e| |a_t| each: 2 x (34 + 2) eps |e| A_t; the sums over the faces one eps per face more on the running sum (valence <= 50 in
+ * practice; 128 covers it).  The store's u.
+ * Workspace: 24 bytes per (frame, vertex), kept by the handle (a growth synchronises the device once).  Otherwise asynchronous on
+ * `stream`.  n_frames == 0 or n_verts == 0: a successful no-op.  BODYFIT_ERR_INVALID: NULL handle / d_verts / d_grad_normals /
+ * d_grad_verts, a negative n_frames, a stride below 3 n_verts.                                                                 */
+int bodyfit_surface_vertex_normals_vjp_device(bodyfit_surface* s, const float* d_verts, long long verts_frame_stride, int n_frames,
+                                              const float* d_grad_normals, float* d_grad_verts, long long grad_frame_stride,
+                                              void* stream);
 /* The uniform mesh LAPLACIAN of per-vertex fields (k_offsets.hip), the smoothness operator of an offset field's regulariser:
  * field k is [n_verts][3] f32 at d_field + k field_stride (>= 3 n_verts), d_out [n_fields][n_verts][3] f32, dense, not d_field.
  * With n_i the number of faces that hold vertex i (a face that repeats i counted once) and a, b the face's other two corner
@@ -1481,6 +1507,94 @@ int bodyfit_raster_texture_mip_grad_device(bodyfit_raster* r, const int32_t* d_f
                                            long long mip_frame_stride, int max_level, float lod_bias, const float* d_grad_image,
                                            float* d_grad_uv /* may be NULL */, float* d_grad_tex /* may be NULL */,
                                            long long* d_workspace /* may be NULL without d_grad_tex */, void* stream);
+/* LIGHTING OF A RENDER (k_lt_forward, k_light.hip): second-order spherical-harmonic shading, image = albedo x shading(normal).
+ * d_face, d_bary, d_verts (only the corners' z is read), verts_frame_stride and the VOID rule are exactly
+ * bodyfit_raster_shade_device's.  d_normals f32 [n_frames][n_verts][3], normals_frame_stride floats between frames (>= 3 n_verts):
+ * per-vertex normals, bodyfit_surface_vertex_normals_device's or any others; they need not be unit.  d_albedo f32 [n_frames][H][W]
+ * [n_channels], n_channels in 1 .. 4: an image that bodyfit_raster_shade_device or a texture lookup made, background included.
+ * d_light f32 [9][n_channels], light_frame_stride floats between the frames' lights: 0 when the frames share one, else >= 9
+ * n_channels.  Outputs, dense, every element of every frame written whatever the buffers held: d_image f32 [n_frames][H][W]
+ * [n_channels]; unless NULL d_normal f32 [n_frames][H][W][3] and d_shading f32 [n_frames][H][W][n_channels].
+ * DEFINITION, exact from the f32 inputs.  w_a are the shade's weights, formed by the same operations in the same order (bit-equal
+ * to its d_weight before the store).  With n_a the normal of corner a:  m = (w_0 n_0 + w_1 n_1) + w_2 n_2 per component,
+ * l = |m| = sqrt((m_x^2 + m_y^2) + m_z^2), n = m / l = (x, y, z),
+ *   b(n) = (1, x, y, z, x y, x z, y z, x^2 - y^2, 3 z^2 - 1),   s_c = sum_k light[k][c] b_k (ascending k),   image_c = albedo_c s_c.
+ * The pixel is UNLIT iff it is void by the shade's rule, or a component of one of the three corner normals is not finite, or l is 0
+ * or not finite.  An unlit pixel gets image = albedo EXACTLY (the background passes through, bit for bit), normal 0, shading 0.
+ * There is no clamp: a negative s_c is stored as it is.  Light and albedo are plain IEEE.
+ * THE BASIS is the UNNORMALISED polynomial one.  The irradiance of Ramamoorthi and Hanrahan ("An Efficient Representation for
+ * Irradiance Environment Maps", 2001, eq. 13) with real-SH lighting coefficients L_lm and c1 = 0.429043, c2 = 0.511664, c3 = 0.743125,
+ * c4 = 0.886227, c5 = 0.247708 (c3 = 3 c5) is this s with
+ *   light[0] = c4 L_00,  light[1 .. 3] = 2 c2 (L_11, L_1-1, L_10),  light[4 .. 6] = 2 c1 (L_2-2, L_21, L_2-1),  light[7] = c1 L_22,
+ *   light[8] = c5 L_20                                                  (c3 L_20 z^2 - c5 L_20 = c5 L_20 (3 z^2 - 1)).
+ * CONTRACT, with u = 2^-24, eps = 2^-53, k_l = 16, k_c = 256 and per lit pixel c = sum_a w_a |n_a| / l >= 1 (how much the three
+ * corner normals cancel; |.| the Euclidean norm), per channel:
+ *   |image^_c - image_c| <= u |image_c| + k_l eps |albedo_c| sum_k |light_kc| |b_k| + k_c eps c |albedo_c| sum_{k >= 1} |light_kc|,
+ * |shading^_c - s_c| the same without albedo, |normal^ - n| <= u + 32 eps c per component; the decision "lit" is exact unless l
+ * underflows (|m| below 2^-500).
+ * Derivation (every operation f64 and unfused).  w_a: 5 eps (the shade's).  A product w_a n_a: 6 eps; the two sums: |dm| <= 8 eps
+ * sum_a w_a |n_a| per component, sqrt(3) times that in norm: 14 eps c l.  l: the squares, two sums and the root add 2.5 eps to the
+ * 14 eps c l that dm moves it.  A component of n = m / l: 8 c + (14 c + 2.5) + 1 < 32 c eps (c >= 1).  b_k has a gradient of 1-norm
+ * at most 6 on the unit ball (3 z^2 - 1) and at most 4 operations on magnitudes <= 3: |db_k| <= 6 x 32 c eps + 8 eps <= 200 c eps:
+ * the third term, stated as k_c = 256 (b_0 = 1 is exact).  The sum: nine products and eight sums, then the product with albedo: 10 eps
+ * sum |light b|, stated as k_l = 16.  The store rounds once: u |image|.
+ * One thread per pixel, neighbouring lanes on neighbouring columns; a workgroup holds pixels of ONE frame, so the frame's light is
+ * read at wave-uniform addresses (scalar loads), never gathered per lane.  Plain stores, no atomics, no workspace: bit-identical
+ * from run to run, and a frame's outputs depend on that frame only.  Asynchronous on `stream`, no host synchronisation.
+ * n_frames == 0: a successful no-op; n_faces == 0: image = albedo.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative
+ * n_frames, n_channels outside 1 .. 4, a non-zero light stride below 9 n_channels, and with frames to write: NULL d_face / d_bary /
+ * d_albedo / d_light / d_image, NULL d_verts or d_normals (n_faces > 0), a vertex or normal stride below 3 n_verts, 2^39 pixels or
+ * more.                                                                                                                          */
+int bodyfit_raster_light_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                long long verts_frame_stride, const float* d_normals, long long normals_frame_stride,
+                                const float* d_albedo, int n_channels, const float* d_light, long long light_frame_stride,
+                                int n_frames, float* d_image, float* d_normal /* may be NULL */, float* d_shading /* may be NULL */,
+                                void* stream);
+/* THE LIGHTING'S GRADIENTS (k_lt_grad, k_lt_light_sum, k_light.hip) for an upstream G = d_grad_image f32 [n_frames][H][W]
+ * [n_channels]; the other inputs are bodyfit_raster_light_device's and the pixel is evaluated again by the same device function.
+ * Three results, each skipped when its pointer is NULL:
+ * (a) d_grad_albedo f32 [n_frames][H][W][n_channels]: G_c s_c on a lit pixel, G_c on an unlit one.
+ * (b) d_grad_m f32 [n_frames][H][W][3]: the gradient in the UNNORMALISED interpolated normal m, what the rows VJP
+ *     (bodyfit_surface_rows_vjp_device with the shade's weights) carries to the corner normals.  With t_c = G_c albedo_c, q_k = sum_c
+ *     t_c light[k][c] (ascending c),  g_n = sum_k q_k grad b_k(n):
+ *       g_x = ((q_1 + y q_4) + z q_5) + 2 x q_7,   g_y = ((q_2 + x q_4) + z q_6) - 2 y q_7,   g_z = ((q_3 + x q_5) + y q_6) + 6 z q_8,
+ *     g_m = (g_n - n (n . g_n)) / l;  0 on an unlit pixel.
+ * (c) d_grad_light f32 [n_frames][9][n_channels], ALWAYS per frame (a caller with a shared light adds the frames):
+ *     g*[f][k][c] = sum over the lit pixels of frame f of t_c b_k(n).
+ * HOW (c) IS SUMMED: a store pass and a fixed-order sum pass, no float atomics.  bodyfit_light_grad_layout (host only, no GPU) gives
+ * the CHUNK: 256 P pixels, P the smallest power of two with at most 256 chunks per frame, at most 64: a function of H W only.  A
+ * workgroup owns one chunk of one frame (chunks never straddle frames); thread j takes the pixels chunk + i 256 + j in ascending i
+ * into its own f64 sums, the lanes of a wave are added by a butterfly (partners at distance 32, 16 .. 1: every lane holds the same
+ * tree), the four waves in ascending order, and the chunk's [9][n_channels] f64 partial is stored into d_workspace, f64 [n_frames]
+ * [n_chunks][9][n_channels] (*workspace_doubles of them; every one that is read is written first).  A second kernel adds a frame's
+ * partials in ascending chunk order and rounds ONCE.  So d_grad_light is bit-identical from run to run, and a frame's 9 n_channels
+ * numbers are a function of that frame's data and of (H, W, n_channels) only: not of n_frames, of the frame's place in the batch
+ * or of the device's CU count.  A non-finite G or albedo on a lit pixel gives a non-finite coefficient in THAT frame only; an
+ * unlit pixel adds nothing (it is skipped, not multiplied by 0).  1920 x 1080: P = 32, 254 chunks of 8,192 pixels.
+ * CONTRACT, with u, eps, c, k_l, k_c of the lighting, k_m = 4096, k_r0 = 80, Q = sum_{k >= 1} sum_c |t_c light_kc|:
+ *   (a) |ga^_c - ga_c| <= u |ga_c| + |G_c| (k_l eps sum_k |light_kc| |b_k| + k_c eps c sum_{k >= 1} |light_kc|) on a lit pixel; exact
+ *       on an unlit one;
+ *   (b) |gm^ - g_m| <= u |g_m| + k_m eps c Q / l per component;
+ *   (c) |g^ - g*| <= u |g*| + eps sum over the frame's lit pixels of |t_c| ((k_r0 + n_chunks) |b_k| + k_c c).
+ * Derivation.  (a): the lighting's, with G for albedo.  (b): |dn| <= 32 c eps per component; the second derivatives of the b_k are
+ * at most 6 and a component of g_n has four terms: |dg_n| <= (18 x 32 c + 72) eps Q <= 650 c eps Q, |g_n| <= 10.4 Q in norm; the
+ * projection: 2 x 1.8 x 32 c x 10.4 + 3 x 650 c < 3200 c eps Q; the division by l, which is 17 c eps off: 360 c eps Q more.  Together
+ * below 4096 c eps Q / l.  (c): a term t_c b_k: two products and db_k <= k_c c eps; a sum of f64 numbers added along a path of at
+ * most P + 6 + 3 + n_chunks <= 73 + n_chunks additions; the store's u.
+ * One workgroup per chunk, plain stores.  Asynchronous on `stream`, NO host synchronisation and no allocation: the caller owns
+ * d_workspace.  n_frames == 0, or all three outputs NULL: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): every
+ * case of bodyfit_raster_light_device but d_image's, and with frames to write: NULL d_grad_image, d_grad_light without
+ * d_workspace.  bodyfit_light_grad_layout: negative counts, n_channels outside 1 .. 4.
+ * NOT BUILT: specular terms, shadows and ambient occlusion, SH orders above 2, the term's normal equations, the C++ mirror header's
+ * entries.                                                                                                                      */
+int bodyfit_light_grad_layout(long long pixels_per_frame, int n_channels, int n_frames, long long* chunk_pixels /* may be NULL */,
+                              long long* n_chunks /* may be NULL */, long long* workspace_doubles /* may be NULL */);
+int bodyfit_raster_light_grad_device(bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
+                                     long long verts_frame_stride, const float* d_normals, long long normals_frame_stride,
+                                     const float* d_albedo, int n_channels, const float* d_light, long long light_frame_stride,
+                                     int n_frames, const float* d_grad_image, float* d_grad_albedo /* may be NULL */,
+                                     float* d_grad_m /* may be NULL */, float* d_grad_light /* may be NULL */,
+                                     double* d_workspace /* may be NULL without d_grad_light */, void* stream);
 /* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster.hip): the coverage of a render as a smooth
  * function of the vertices, after Laine et al., "Modular Primitives for High-Performance Differentiable Rendering" (2020).  Only
  * COVERAGE carries a gradient here: how an attribute interpolates inside a face as its corners move is not part of it.
