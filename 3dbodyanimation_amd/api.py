@@ -337,6 +337,12 @@ def load_library():
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.bodyfit_surface_vertex_normals_vjp_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p,
                                                               C.c_longlong, C.c_void_p]
+    lib.bodyfit_volume_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_void_p)]
+    lib.bodyfit_volume_destroy.argtypes = [C.c_void_p]
+    lib.bodyfit_volume_destroy.restype = None
+    lib.bodyfit_volume_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p,
+                                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1356,6 +1362,46 @@ class Raster:
     def close(self):
         if getattr(self, "h", None):
             load_library().bodyfit_raster_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Volume:
+    """The geometry of a scalar volume [nz, ny, nx] f32 (x fastest), voxel (k, j, i) at origin + (i sx, j sy, k sz), and its
+    trilinear sampler (bodyfit_volume_*, csrc/k_volume.hip; the definition and its contract: include/bodyfit.h).  The handle holds
+    no device memory: the voxels are an argument of every call."""
+
+    def __init__(self, device: int, dims, origin, spacing):
+        nx, ny, nz = (int(n) for n in dims)
+        o, s = _c64(origin).reshape(-1), _c64(spacing).reshape(-1)
+        if o.shape[0] != 3 or s.shape[0] != 3:
+            raise ValueError("dims is (nx, ny, nz), origin and spacing are 3 floats")
+        h = C.c_void_p()
+        _check(load_library().bodyfit_volume_create(int(device), nx, ny, nz, _d(o), _d(s), C.byref(h)))
+        self.h = h
+        self.device = device
+        self.nx, self.ny, self.nz = nx, ny, nz
+        self.origin, self.spacing = tuple(float(a) for a in o), tuple(float(a) for a in s)
+
+    def sample_device(self, d_points_ptr: int, points_frame_stride: int, n_points: int, n_frames: int, d_volume_ptr: int,
+                      volume_frame_stride: int, d_gate_ptr: int | None, d_value_ptr: int, d_valid_ptr: int,
+                      d_grad_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_volume_sample_device: the volumes [nz, ny, nx] f32 (volume_frame_stride elements between frames, 0: one for all)
+        read trilinearly at points [F, n_points, 3] f32: value [F, n_points] f32, valid [F, n_points] u8 and, unless None, grad
+        [F, n_points, 3] f32 = (d/dx, d/dy, d/dz) in world units; gate u8 [F, n_points] or None.  Asynchronous on `stream`, no host
+        synchronisation."""
+        _check(load_library().bodyfit_volume_sample_device(self.h, d_points_ptr, int(points_frame_stride), int(n_points),
+                                                           int(n_frames), d_volume_ptr, int(volume_frame_stride), d_gate_ptr,
+                                                           d_value_ptr, d_valid_ptr, d_grad_ptr, stream))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().bodyfit_volume_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -12,6 +12,7 @@ describes what it holds:
     texture      render_texture, TexturedPhotometricTerm, bake_texture; with mipmaps (a trilinear lookup at the pixel's level of
                  detail and its gradients): texture.render_texture_mip and TexturedPhotometricTerm.mipmaps()
     lighting     lighting.vertex_normals (differentiable), sh_basis, shade, LitPhotometricTerm (names reached through the module)
+    volume       volume.sample_volume, voxelize_sdf, grid_points, VolumeTerm: signed-distance volumes (names reached through the module)
     _common      what they share: point sets, the kept handles (one cache each), the argument checks, the row helpers
 
 Every public name of the recorded surface (tests/golden/torch_layer_surface.json) is importable from here, and so are the private

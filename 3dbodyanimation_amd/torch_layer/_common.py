@@ -194,6 +194,22 @@ def _raster_handle(device_index: int, n_verts: int, faces, size):
                             lambda f: api.Raster(device_index, n_verts, f, W, H))
 
 
+_volume_handles: dict[tuple, object] = {}   # (device, (nx, ny, nz), origin, spacing) -> api.Volume; the last _SURFACE_CACHE in use
+
+
+def _volume_handle(device_index: int, dims, origin, spacing):
+    """The api.Volume of (device, geometry): dims = (nx, ny, nz), origin and spacing three floats each.  The handle owns nothing
+    on the device; it is kept so that an evaluation does not create one."""
+    key = (device_index, tuple(int(n) for n in dims), tuple(float(a) for a in origin), tuple(float(a) for a in spacing))
+    h = _volume_handles.pop(key, None)
+    if h is None:
+        h = api.Volume(device_index, key[1], key[2], key[3])
+    _volume_handles[key] = h                        # (most recently used last)
+    while len(_volume_handles) > _SURFACE_CACHE:
+        _volume_handles.pop(next(iter(_volume_handles)))
+    return h
+
+
 _NO_FACES = np.zeros((0, 3), np.int32)
 
 

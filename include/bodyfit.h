@@ -1694,6 +1694,69 @@ int bodyfit_raster_edge_rows_device(bodyfit_raster* r, const float* d_verts, lon
  * longest tile list.                                                                                                          */
 int bodyfit_raster_last_bins(bodyfit_raster* r, long long* n_entries, int* longest);
 
+/* SIGNED-DISTANCE VOLUMES (k_vol_sample, k_volume.hip; the host side: api_volume.hip): a scalar volume read trilinearly at the
+ * points of a cloud, with the exact spatial gradient there: the 3-D counterpart of bodyfit_raster_sample_device.  It is what a body
+ * is measured against when the world around it is given as a distance field: a pre-scanned scene, a fused TSDF, an object.
+ * The handle holds the GEOMETRY only, as the raster handle holds an image size: nx, ny, nz >= 1 voxels with nx ny nz < 2^31, the
+ * position `origin` of voxel (0, 0, 0) and the `spacing` between voxels per axis (finite; spacing > 0; the axes may differ).  It
+ * owns no device memory and no workspace: calls on one handle need no ordering.  BODYFIT_ERR_INVALID: NULL out / origin / spacing,
+ * a dimension below 1, 2^31 voxels or more, a non-finite origin, a spacing that is not finite and positive or whose reciprocal is
+ * not a normal f64 number.                                                                                                       */
+typedef struct bodyfit_volume bodyfit_volume;
+int bodyfit_volume_create(int device, int nx, int ny, int nz, const double origin[3], const double spacing[3],
+                          bodyfit_volume** out);
+void bodyfit_volume_destroy(bodyfit_volume* h);
+/* d_points f32 [n_frames][n_points][3], points_frame_stride floats between frames (>= 3 n_points: bodyfit_device_views.cloud is
+ * used in place).  d_volume f32 [nz][ny][nx], x fastest; volume_frame_stride ELEMENTS between the frames' volumes: 0 when the frames
+ * share one, else >= nx ny nz.  d_gate u8 [n_frames][n_points] or NULL.  Outputs d_value f32 [n_frames][n_points], d_valid u8
+ * [n_frames][n_points] and, unless NULL, d_grad f32 [n_frames][n_points][3] = (d/dx, d/dy, d/dz) in WORLD units (value per metre
+ * when the points are metres).  Every element is written; a dead point gets 0 everywhere and valid 0.
+ * DEFINITION.  Voxel (k, j, i) sits at origin + (i sx, j sy, k sz).  Grid coordinates g = (p - origin) / spacing, per axis, in f64.
+ * A point is LIVE iff its coordinates are finite, its gate byte is non-zero (or d_gate is NULL), 0 <= g_a <= n_a - 1 on every axis,
+ * and ALL EIGHT VOXELS OF ITS CELL ARE FINITE: a TSDF marks unobserved space with NaN or inf, and a vertex there costs nothing
+ * rather than poison a sum.  The cell is bilinear_cell's on three axes: i0 = min(floor(gx), max(nx - 2, 0)), i1 = min(i0 + 1,
+ * nx - 1), a = gx - i0, and (j0, j1, b) in y, (k0, k1, c) in z alike.  With V[dk][dj][di] = volume[k_dk][j_dj][i_di],
+ *   value = sum over (dk, dj, di) of  (di ? a : 1 - a) (dj ? b : 1 - b) (dk ? c : 1 - c) V[dk][dj][di],
+ *   d/dx  = ((1-b)(1-c) (V001 - V000) + b (1-c) (V011 - V010) + (1-b) c (V101 - V100) + b c (V111 - V110)) / sx,
+ *   d/dy  = ((1-a)(1-c) (V010 - V000) + a (1-c) (V011 - V001) + (1-a) c (V110 - V100) + a c (V111 - V101)) / sy,
+ *   d/dz  = ((1-a)(1-b) (V100 - V000) + a (1-b) (V101 - V001) + (1-a) b (V110 - V010) + a b (V111 - V011)) / sz:
+ * the exact derivative of the trilinear patch of the cell, over the spacing (at g_a = n_a - 1 the last cell's, taken from inside;
+ * an axis of length 1 has i1 = i0: derivative 0).
+ * CONTRACT, with u = 2^-24, E = max(nx, ny, nz), delta = 2^-50 E (in voxels) and M the largest |voxel| among the voxels of the
+ * exact cell and of the returned cell:
+ *   (a) a point that passes the other tests and lies at least delta inside the box [0, n_a - 1]^3 is tested on the voxels of a cell
+ *       K whose closed support is within delta of the exact g, and is live iff K's eight are finite; a point returned live lies
+ *       within delta of the box; the tests on the gate and on finiteness (of the point, of K's voxels) are exact, and so is
+ *       g_a = 0 for a coordinate that equals the origin's (the only way onto an axis of length 1);
+ *   (b) |value^ - T(g)| <= u |T| + 2^-46 E M, T the continuous piecewise-trilinear field through the voxels (where the exact
+ *       cell holds a voxel that is not finite and K does not: K's patch, extended);
+ *   (c) each returned derivative is within u |g_K| + 2^-46 E M / spacing of the derivative g_K of K's patch at g, K the cell of (a).
+ * Derivation (eps = 2^-53; every operation f64 and unfused).  g^: an f32 coordinate is exact in f64; the kernel multiplies by
+ * 1 / spacing, formed once on the host, where the definition divides: the reciprocal, the difference and the product round once
+ * each, 3 eps |g| (1 + eps)^2 < 2^-51 E for a point within delta of the box: inside delta.  The comparisons and
+ * floor act on g^, which gives (a), and the returned cell K holds g^ in its closed support.  a = g^ - i0 is exact (Sterbenz, or
+ * i0 = 0 and a = g^).  T is continuous and, inside a cell, of slope at most 2 M per voxel in each coordinate.  Let c be g clamped
+ * onto K's closed support: c lies in the exact cell too, within delta of g per axis, and within delta of g^: |T(g) - T(c)| <= 6 M
+ * delta in the exact cell and |T(c) - T(g^)| <= 6 M delta in K, together 12 M delta < 2^-46.4 E M.  The patch evaluated in f64:
+ * three 1 - x, two products per weight, one product with the voxel, three levels of sums: below 16 eps M = 2^-49 M.  Together
+ * below 2^-46 E M; the store rounds once: u |T|.  A derivative of K's patch in grid units is bilinear in the other two
+ * coordinates with slope at most 4 M in each: 8 M delta = 2^-47 E M for the move from g to g^; a difference of two voxels rounds
+ * once, two products, two levels of sums: below 16 eps M; the product with 1 / spacing twice more: 2 eps (2 M).  Over the spacing,
+ * together below 2^-46 E M / spacing; the store's u |g_K|.  (A result below 2^-126 in magnitude is stored to a multiple of 2^-149:
+ * with M below 2^-100 the statement lacks that term.)
+ * One thread per (frame, point); the eight voxels are gathered before anything is combined.  Plain stores, no atomics, no
+ * workspace: bit-identical from run to run, a frame's outputs depend on that frame only (bit-identical whatever n_frames), and
+ * d_value / d_valid do not depend on whether d_grad is given.  Asynchronous on `stream`, no host synchronisation.  n_frames == 0 or
+ * n_points == 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames or n_points, and
+ * with points to write: NULL d_points / d_volume / d_value / d_valid, a point stride below 3 n_points, a volume stride that is
+ * neither 0 nor >= nx ny nz, 2^39 points or more.
+ * NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, a 3-D distance
+ * transform, TSDF integration from depth maps, and the entries of the C++ mirror header.                                        */
+int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long long points_frame_stride, long long n_points,
+                                 int n_frames, const float* d_volume, long long volume_frame_stride,
+                                 const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
+                                 float* d_grad /* may be NULL */, void* stream);
+
 /* kernels launched by this process through the library so far (benchmarks: launches per LM iteration) */
 long bodyfit_launch_count(void);
 const char* bodyfit_last_error(void);
