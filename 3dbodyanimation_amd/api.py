@@ -343,6 +343,9 @@ def load_library():
     lib.bodyfit_volume_destroy.restype = None
     lib.bodyfit_volume_sample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p,
                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_volume_integrate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                                    C.POINTER(C.c_double), C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1398,6 +1401,22 @@ class Volume:
         _check(load_library().bodyfit_volume_sample_device(self.h, d_points_ptr, int(points_frame_stride), int(n_points),
                                                            int(n_frames), d_volume_ptr, int(volume_frame_stride), d_gate_ptr,
                                                            d_value_ptr, d_valid_ptr, d_grad_ptr, stream))
+
+    def integrate_device(self, d_depth_ptr: int | None, depth_frame_stride: int, height: int, width: int, n_frames: int, intr,
+                         d_pose_ptr: int | None, trunc: float, z_near: float, max_weight: float, reset: bool, d_tsdf_ptr: int,
+                         d_weight_ptr: int, volume_frame_stride: int = 0, stream: int | None = None):
+        """bodyfit_volume_integrate_device: the depth maps [n_frames, height, width] f32 (metres along the optical axis,
+        depth_frame_stride floats between frames), seen through intr = (fx, fy, cx, cy) from the world -> camera maps d_pose
+        [n_frames, 12] f64 (None: the identity), fused in ascending order into the state (tsdf, weight) [nz, ny, nx] f32 of this
+        geometry: volume_frame_stride 0 into one volume, >= nx ny nz frame f into volume f.  reset: start from the empty state
+        (NaN, 0) without reading the buffers.  max_weight inf: no cap.  Asynchronous on `stream`, no host synchronisation."""
+        k = None if intr is None else _c64(intr).reshape(-1)
+        if k is not None and k.shape[0] != 4:
+            raise ValueError("intr is (fx, fy, cx, cy)")
+        _check(load_library().bodyfit_volume_integrate_device(self.h, d_depth_ptr, int(depth_frame_stride), int(height), int(width),
+                                                              int(n_frames), None if k is None else _d(k), d_pose_ptr, float(trunc),
+                                                              float(z_near), float(max_weight), 1 if reset else 0, d_tsdf_ptr,
+                                                              d_weight_ptr, int(volume_frame_stride), stream))
 
     def close(self):
         if getattr(self, "h", None):

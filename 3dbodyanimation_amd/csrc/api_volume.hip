@@ -1,5 +1,5 @@
-// The C ABI of the signed-distance volumes (include/bodyfit.h: bodyfit_volume_create / _destroy / _sample_device): the handle, the
-// argument checks and the one launch (k_volume.hip through volume.h).
+// The C ABI of the signed-distance volumes (include/bodyfit.h: bodyfit_volume_create / _destroy / _sample_device /
+// _integrate_device): the handle, the argument checks and the one launch of each call (k_volume.hip, k_tsdf.hip through volume.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -69,6 +69,48 @@ int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long 
   a.volume = d_volume; a.volume_stride = volume_frame_stride;
   a.gate = d_gate; a.value = d_value; a.valid = d_valid; a.grad = d_grad;
   launch_volume_sample(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_integrate_device(bodyfit_volume* h, const float* d_depth, long long depth_frame_stride, int height, int width,
+                                    int n_frames, const double intr[4], const double* d_pose, double trunc, double z_near,
+                                    double max_weight, int reset, float* d_tsdf, float* d_weight, long long volume_frame_stride,
+                                    void* stream) {
+  using namespace bodyfit;
+  const char* fn = "bodyfit_volume_integrate_device";
+  if (!h) return vol_invalid(fn, "handle is NULL");
+  if (n_frames < 0) return vol_invalid(fn, "negative n_frames");
+  if (height < 1 || width < 1) return vol_invalid(fn, "height or width below 1");
+  if ((long long)height * width >= (1ll << 31)) return vol_invalid(fn, "2^31 pixels or more");
+  if (depth_frame_stride < (long long)height * width) return vol_invalid(fn, "depth_frame_stride below height width");
+  const long long n_voxels = (long long)h->nx * h->ny * h->nz;
+  if (volume_frame_stride != 0 && volume_frame_stride < n_voxels)
+    return vol_invalid(fn, "volume_frame_stride is neither 0 (one volume) nor >= nx ny nz");
+  if (!std::isfinite(trunc) || !(trunc > 0.0)) return vol_invalid(fn, "trunc must be finite and positive");
+  if (!std::isfinite(z_near) || z_near < 0.0) return vol_invalid(fn, "z_near must be finite and not negative");
+  if (!(max_weight > 0.0)) return vol_invalid(fn, "max_weight must be positive (+inf: no cap)");
+  if (!intr) return vol_invalid(fn, "intr is NULL");
+  for (int a = 0; a < 4; ++a)
+    if (!std::isfinite(intr[a])) return vol_invalid(fn, "the intrinsics must be finite");
+  if (intr[0] == 0.0 || intr[1] == 0.0) return vol_invalid(fn, "fx or fy is zero");
+  // what there is to do: every frame's volume, or the one volume when there is a frame to fuse or the empty state to write
+  const long long n_volumes = volume_frame_stride != 0 ? n_frames : (n_frames > 0 || reset ? 1 : 0);
+  if (n_volumes == 0) return BODYFIT_OK;
+  if (!d_tsdf || !d_weight || (n_frames > 0 && !d_depth)) return vol_invalid(fn, "d_depth, d_tsdf or d_weight is NULL");
+  const long long chunks = (n_voxels + 255) / 256;
+  if (chunks * n_volumes >= (1ll << 31)) return vol_invalid(fn, "2^31 workgroups or more in one call");
+  HIP_TRY(hipSetDevice(h->device));
+  TsdfArgs a;
+  a.nx = h->nx; a.ny = h->ny; a.nz = h->nz;
+  a.n_voxels = (unsigned)n_voxels; a.chunks = (unsigned)chunks;
+  for (int k = 0; k < 3; ++k) { a.origin[k] = h->origin[k]; a.spacing[k] = h->spacing[k]; }
+  a.depth = d_depth; a.depth_stride = depth_frame_stride; a.H = height; a.W = width; a.F = n_frames;
+  a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
+  a.pose = d_pose;
+  a.trunc = trunc; a.z_near = z_near; a.max_weight = max_weight; a.reset = reset;
+  a.tsdf = d_tsdf; a.weight = d_weight; a.volume_stride = volume_frame_stride;
+  launch_tsdf_integrate(a, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

@@ -2,7 +2,8 @@
 or a per-frame distance volume of a scan, an object to touch).  The names are reached through the module:
 
     from 3dbodyanimation_amd.torch_layer import volume
-    sdf = volume.voxelize_sdf(scene_verts, scene_faces, origin, spacing, dims)          # once; or a TSDF from elsewhere
+    sdf = volume.voxelize_sdf(scene_verts, scene_faces, origin, spacing, dims)          # once, from a scene that is a mesh
+    sdf, weight = volume.integrate_tsdf(depth, intr, origin, spacing, dims, trunc=0.05, pose=world_to_camera)   # or from depth maps
     value, valid = volume.sample_volume(sdf, origin, spacing, verts)                    # [F, V] f32, differentiable in verts
     floor = volume.VolumeTerm(sdf, origin, spacing, mode="inside")                      # penetration: only inside costs
     soles = volume.VolumeTerm(sdf, origin, spacing, mode="zero", vertex_ids=sole_ids)   # contact: pulled to the zero level
@@ -14,8 +15,13 @@ the scene's size, and the exact derivative of the cell's patch in world units; i
 bounds).  A point outside the volume, a gated point and a point whose cell holds a voxel that is not finite (a TSDF's unobserved
 space) is dead: value 0, no gradient, no cost.
 
+integrate_tsdf is bodyfit_volume_integrate_device (k_tsdf.hip: one lane per voxel, the running average of the projective distance
+along the optical axis, the state in registers over the frames of a call and rounded to f32 after each, so that one call with F
+frames is F calls with one, bit for bit).  It produces what the chain above consumes: unobserved voxels are (NaN, 0).
+
 NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, a 3-D distance
-transform, TSDF integration from depth maps.
+transform; for the fusion: the Euclidean ray length as the measure, a bilinear depth lookup, per-pixel weights, colour volumes,
+surface extraction.
 """
 from __future__ import annotations
 
@@ -125,6 +131,82 @@ def grid_points(origin, spacing, dims, device) -> torch.Tensor:
     ax = [torch.arange(n, dtype=torch.float64, device=device) * float(s[a]) + float(o[a]) for a, n in enumerate((nx, ny, nz))]
     z, y, x = torch.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
     return torch.stack((x, y, z), dim=-1).to(torch.float32)
+
+
+def _check_depth(depth):
+    """the checked depth maps [F, H, W] f32 on the GPU and their frame stride; a view whose [H, W] blocks are dense is used in place"""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or not depth.is_cuda:
+        raise TypeError("depth must be a float32 tensor on the GPU")
+    if depth.ndim != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        raise ValueError(f"depth must be [F, H, W] with H, W >= 1, got {tuple(depth.shape)}")
+    F, H, W = depth.shape
+    d = depth.detach()
+    if not (d.stride(2) == 1 and d.stride(1) == W and (F <= 1 or d.stride(0) >= H * W)):
+        d = d.contiguous()
+    return d, (d.stride(0) if F > 1 else H * W)
+
+
+def _check_pose(pose, depth):
+    if pose is None:
+        return None
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64:
+        raise TypeError("pose must be a float64 tensor on the GPU of depth, or None")
+    if pose.device != depth.device:
+        raise ValueError(f"pose is on {pose.device}, depth on {depth.device}")
+    F = depth.shape[0]
+    if tuple(pose.shape) not in ((F, 3, 4), (F, 12)):
+        raise ValueError(f"pose must be [F, 3, 4] or [F, 12] with F = {F}, got {tuple(pose.shape)}")
+    return pose.detach().reshape(F, 12).contiguous()
+
+
+def integrate_tsdf(depth: torch.Tensor, intr, origin, spacing, dims, trunc: float, pose: torch.Tensor | None = None,
+                   z_near: float = 0.1, max_weight: float | None = None, state=None, per_frame: bool = False):
+    """TSDF fusion: the depth maps depth [F, H, W] f32 (metres along the optical axis, the depth of render_depth and of the depth
+    terms; 0, a negative value, NaN or inf: a pixel that holds nothing), seen through intr = (fx, fy, cx, cy) from the world ->
+    camera maps pose ([F, 3, 4] or [F, 12] f64 on depth's device, [A | t] row-major; None: the identity), integrated into a
+    volume of dims = (nx, ny, nz), origin and spacing as sample_volume's: (tsdf, weight), f32 [nz, ny, nx] each, the frames fused
+    in ascending order, or with per_frame=True [F, nz, ny, nx], frame f alone in volume f.  A voxel in front of z_near that projects
+    onto a pixel with a depth d takes s = d - q_z into its running average unless s < -trunc (hidden): D' = (W D + min(s, trunc)) /
+    (W + 1), W' = min(W + 1, max_weight) (None: no cap), both rounded to f32 after every frame: D is positive in front of the
+    surface, the sign of voxelize_sdf.  A voxel no frame has updated is (NaN, 0): sample_volume and VolumeTerm read it as dead.
+
+    state=(tsdf, weight) continues an integration ([nz, ny, nx], or [F, nz, ny, nx] with per_frame); the result is a new pair, the
+    arguments are left as they are, and fusing F frames at once gives the bits of fusing them one call at a time.  One launch of
+    bodyfit_volume_integrate_device (include/bodyfit.h has the definition and its bounds) on torch.cuda.current_stream(), without
+    a host synchronisation.  No gradient."""
+    d, stride = _check_depth(depth)
+    F, H, W = d.shape
+    nx, ny, nz = (int(n) for n in dims)
+    if min(nx, ny, nz) < 1:
+        raise ValueError(f"dims must be (nx, ny, nz) >= 1, got {(nx, ny, nz)}")
+    shape = (F, nz, ny, nx) if per_frame else (nz, ny, nx)
+    k = tuple(float(a) for a in np.asarray(intr, np.float64).reshape(-1))
+    if len(k) != 4:
+        raise ValueError("intr is (fx, fy, cx, cy)")
+    p = _check_pose(pose, d)
+    if state is None:
+        tsdf = torch.empty(shape, dtype=torch.float32, device=d.device)
+        weight = torch.empty(shape, dtype=torch.float32, device=d.device)
+    else:
+        if not isinstance(state, (tuple, list)) or len(state) != 2:
+            raise TypeError("state is the pair (tsdf, weight) of an earlier call")
+        pair = []
+        for name, t in zip(("tsdf", "weight"), state):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+                raise TypeError(f"state's {name} must be a float32 tensor on the GPU")
+            if t.device != d.device:
+                raise ValueError(f"state's {name} is on {t.device}, depth on {d.device}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"state's {name} must be {shape}, got {tuple(t.shape)}")
+            pair.append(t.detach().clone(memory_format=torch.contiguous_format))
+        tsdf, weight = pair
+    _, o, s = _geometry(tsdf, origin, spacing)
+    handle = _volume_handle(d.device.index, (nx, ny, nz), o, s)
+    with torch.cuda.device(d.device):
+        handle.integrate_device(d.data_ptr() if F > 0 else None, stride, H, W, F, k, p.data_ptr() if p is not None and F > 0 else None,
+                                float(trunc), float(z_near), float("inf") if max_weight is None else float(max_weight),
+                                state is None, tsdf.data_ptr(), weight.data_ptr(), nx * ny * nz if per_frame else 0, stream=_stream())
+    return tsdf, weight
 
 
 def voxelize_sdf(verts: torch.Tensor, faces, origin, spacing, dims, chunk: int = 1 << 18) -> torch.Tensor:

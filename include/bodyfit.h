@@ -1751,11 +1751,62 @@ void bodyfit_volume_destroy(bodyfit_volume* h);
  * with points to write: NULL d_points / d_volume / d_value / d_valid, a point stride below 3 n_points, a volume stride that is
  * neither 0 nor >= nx ny nz, 2^39 points or more.
  * NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, a 3-D distance
- * transform, TSDF integration from depth maps, and the entries of the C++ mirror header.                                        */
+ * transform, and the entries of the C++ mirror header.                                                                          */
 int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long long points_frame_stride, long long n_points,
                                  int n_frames, const float* d_volume, long long volume_frame_stride,
                                  const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
                                  float* d_grad /* may be NULL */, void* stream);
+/* TSDF FUSION (k_tsdf_integrate, k_tsdf.hip): depth maps integrated into a truncated signed-distance volume of the handle's
+ * geometry, the volume that bodyfit_volume_sample_device reads.  d_depth f32 [n_frames][height][width] metres ALONG THE OPTICAL
+ * AXIS (the depth of bodyfit_raster_render_device and of the depth terms), depth_frame_stride floats between frames (>= height
+ * width); intr = (fx, fy, cx, cy), pixel (i, j) at (u, v) = (j, i); d_pose f64 [n_frames][12], row-major [A | t], world -> camera,
+ * or NULL: the identity (orthonormality is not checked: the definition is in q = A p + t).  d_tsdf / d_weight f32 [nz][ny][nx]:
+ * volume_frame_stride 0: every frame is fused into ONE volume, in ascending order; >= nx ny nz: frame f goes into volume f alone
+ * (the per-frame distance volumes of a moving subject).  reset != 0: the buffers' contents are ignored, the start state is empty.
+ * DEFINITION.  The state of a voxel is (D, W): D the truncated signed distance in metres, POSITIVE in front of the surface (the
+ * sign of a voxelised scene), W the weight.  A voxel is OBSERVED iff W > 0 and D is finite; any other state, whatever its bits,
+ * is unobserved, and an unobserved voxel is written as (NaN, 0): the sampler's dead voxel.  With p = origin + (i sx, j sy, k sz)
+ * and q = A p + t, frame f updates the voxel iff ALL of (each false on a NaN)
+ *   1. q_z > z_near;
+ *   2. with u = fx q_x / q_z + cx, v = fy q_y / q_z + cy, the nearest pixel (i, j) = (floor(v + 1/2), floor(u + 1/2)) has
+ *      0 <= i <= height - 1 and 0 <= j <= width - 1 (tested on the f64 values);
+ *   3. d = depth[f][i][j] is finite and d > 0 (a pixel that holds nothing: 0, negative, NaN, inf);
+ *   4. s = d - q_z >= -trunc (otherwise the voxel is hidden behind the surface and stays as it was).
+ * Then, with sb = min(s, trunc) and (W, W D) = (0, 0) for an unobserved voxel:
+ *   D' = f32((W D + sb) / (W + 1)),   W' = f32(min(W + 1, max_weight)),
+ * each rounded to f32 ONCE PER FRAME, which makes a call with n frames BIT-IDENTICAL to n calls with one frame each and to any
+ * split into consecutive calls that carry (D, W); with a cap the average depends on the order, so the order is part of it.
+ * CONTRACT, with u = 2^-24, eps = 2^-53 and, per voxel and frame, P_a = |origin_a| + index_a s_a, S_r = sum_c |A_rc| P_c + |t_r|
+ * (S_r = P_r without a pose), dd = min(d, 2 (S_z + trunc)):
+ *   (a) decision 1 is exact unless |q_z - z_near| <= 2^-50 S_z, decision 4 unless |s + trunc| <= delta_4 = 2^-50 (S_z + dd);
+ *   (b) for q_z >= 2^-40 S_z each pixel index is floor(x + 1/2 + e) for some |e| <= delta_p(x), x = u or v,
+ *       delta_p(u) = 2^-49 (|fx| (S_x + |q_x / q_z| S_z) / q_z + |u| + |cx| + 1) pixels (v: fy, S_y, q_y, cy); the range test and
+ *       decision 3 are exact for that pixel; for a smaller q_z that passes decision 1 the pixel is not constrained;
+ *   (c) W' is exact, and so is an untouched voxel's state; with D'* the definition's value for SOME decision vector (and pixel)
+ *       admissible under (a) and (b),  |D' - D'*| <= u |D'*| + delta_4 / (W + 1) + 2^-50 (|D| + |sb|) + 2^-149.
+ * Derivation (every operation f64 and unfused; only the two stores round to f32).  p^: a product and a sum, 2 eps P_a.  q^: three
+ * products and three sums, the first term through four roundings, plus |A| carried over p^'s error: below 6.5 eps S_r < 2^-50
+ * S_r, which is (a) for decision 1.  s^ = d - q^_z (d is exact in f64) rounds once more: 6.5 eps S_z + eps (d + S_z) <= 2^-50
+ * (S_z + d); for d > 2 (S_z + trunc) both s and s^ exceed trunc: the decision and sb = trunc are exact, whence dd.  The kernel
+ * forms 1 / q^_z once and multiplies where the definition divides: for q_z >= 2^-40 S_z the move from q to q^ changes fx q_x / q_z
+ * by at most 1.001 x 6.5 eps |fx| (S_x + |q_x / q_z| S_z) / q_z; the product, the reciprocal, the second product, the sum with cx
+ * and the sum with 1/2 round once each: 5 eps |u| + 3 eps |cx| + eps / 2; together below 7 eps (...) < delta_p.  The average:
+ * the product W D, the sum, W + 1 (exact below 2^53) and the quotient: 4 eps |D| + 3 eps |sb| beside sb's own error over W + 1; the
+ * store rounds once, u |D'*|, to a multiple of 2^-149 below 2^-126.
+ * One lane per voxel, x fastest; the state is read at most once (not under reset), kept in registers over the frames and written
+ * once; a frame's camera is wave-uniform; the depth gathers of several frames are issued ahead of their use.  Plain stores, no
+ * atomics, no workspace: bit-identical from run to run.  Asynchronous on `stream`, no host synchronisation, no allocation.
+ * n_frames == 0 launches nothing, unless reset != 0 and volume_frame_stride == 0: then the empty state is written.
+ * BODYFIT_ERR_INVALID (nothing is launched): NULL handle; n_frames < 0; height or width below 1; height width >= 2^31; a depth
+ * stride below height width; a volume stride that is neither 0 nor >= nx ny nz; trunc not finite or not > 0; z_near not finite or
+ * < 0; max_weight not > 0 (+inf: no cap); NULL intr, an intrinsic that is not finite, fx or fy zero; with work to do: NULL
+ * d_tsdf / d_weight, NULL d_depth with frames to fuse, 2^31 workgroups (256 voxels each, per volume) or more.
+ * NOT BUILT: the Euclidean ray length as the measure, a bilinear depth lookup, per-pixel weights, colour volumes, the gradient
+ * in the voxels, surface extraction, and the entry of the C++ mirror header.                                                   */
+int bodyfit_volume_integrate_device(bodyfit_volume* h, const float* d_depth, long long depth_frame_stride, int height, int width,
+                                    int n_frames, const double intr[4], const double* d_pose /* [n_frames][12] or NULL */,
+                                    double trunc, double z_near, double max_weight, int reset, float* d_tsdf, float* d_weight,
+                                    long long volume_frame_stride, void* stream);
 
 /* kernels launched by this process through the library so far (benchmarks: launches per LM iteration) */
 long bodyfit_launch_count(void);
