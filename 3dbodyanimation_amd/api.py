@@ -1089,7 +1089,7 @@ class Overlay:
 class Raster:
     """Depth and face-id render of the posed mesh on the device, face / vertex visibility from a face-id image, per-vertex
     attributes shaded over a render and images sampled at projected points
-    (bodyfit_raster_*, csrc/k_raster.hip; the definition and its contract: include/bodyfit.h).  The handle holds one topology
+    (bodyfit_raster_*, csrc/k_raster*.hip; the definition and its contract: include/bodyfit.h).  The handle holds one topology
     (faces: int32 [n_faces, 3] with ids in [0, n_verts)), one image size and the workspace; calls on one handle must be
     ordered (one stream, or events)."""
 

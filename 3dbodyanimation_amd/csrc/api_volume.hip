@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <string>
 
 #include "../../include/bodyfit.h"
 #include "host_state.h"
@@ -15,25 +14,21 @@ struct bodyfit_volume {
   double origin[3] = {0.0, 0.0, 0.0}, spacing[3] = {1.0, 1.0, 1.0};
 };
 
-namespace {
-int vol_invalid(const char* fn, const char* what) {
-  return bodyfit_internal_fail(BODYFIT_ERR_INVALID, (std::string(fn) + ": " + what).c_str());
-}
-}  // namespace
+using bodyfit::invalid_arg;
 
 extern "C" {
 
 int bodyfit_volume_create(int device, int nx, int ny, int nz, const double origin[3], const double spacing[3],
                           bodyfit_volume** out) {
   const char* fn = "bodyfit_volume_create";
-  if (!out) return vol_invalid(fn, "out is NULL");
-  if (!origin || !spacing) return vol_invalid(fn, "origin or spacing is NULL");
-  if (nx < 1 || ny < 1 || nz < 1) return vol_invalid(fn, "a dimension below 1");
-  if ((long long)nx * ny >= (1ll << 31) || (long long)nx * ny * nz >= (1ll << 31)) return vol_invalid(fn, "2^31 voxels or more");
+  if (!out) return invalid_arg(fn, "out is NULL");
+  if (!origin || !spacing) return invalid_arg(fn, "origin or spacing is NULL");
+  if (nx < 1 || ny < 1 || nz < 1) return invalid_arg(fn, "a dimension below 1");
+  if ((long long)nx * ny >= (1ll << 31) || (long long)nx * ny * nz >= (1ll << 31)) return invalid_arg(fn, "2^31 voxels or more");
   for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(origin[a])) return vol_invalid(fn, "the origin must be finite");
-    if (!(spacing[a] > 0.0) || !std::isfinite(spacing[a])) return vol_invalid(fn, "the spacings must be finite and positive");
-    if (!std::isnormal(1.0 / spacing[a])) return vol_invalid(fn, "a spacing whose reciprocal is not a normal f64 number");
+    if (!std::isfinite(origin[a])) return invalid_arg(fn, "the origin must be finite");
+    if (!(spacing[a] > 0.0) || !std::isfinite(spacing[a])) return invalid_arg(fn, "the spacings must be finite and positive");
+    if (!std::isnormal(1.0 / spacing[a])) return invalid_arg(fn, "a spacing whose reciprocal is not a normal f64 number");
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
@@ -52,14 +47,14 @@ int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long 
                                  float* d_value, uint8_t* d_valid, float* d_grad, void* stream) {
   using namespace bodyfit;
   const char* fn = "bodyfit_volume_sample_device";
-  if (!h) return vol_invalid(fn, "handle is NULL");
-  if (n_frames < 0 || n_points < 0) return vol_invalid(fn, "negative n_frames or n_points");
+  if (!h) return invalid_arg(fn, "handle is NULL");
+  if (n_frames < 0 || n_points < 0) return invalid_arg(fn, "negative n_frames or n_points");
   if (n_frames == 0 || n_points == 0) return BODYFIT_OK;
-  if (!d_points || !d_volume || !d_value || !d_valid) return vol_invalid(fn, "d_points, d_volume, d_value or d_valid is NULL");
-  if (points_frame_stride < 3 * n_points) return vol_invalid(fn, "points_frame_stride below 3 n_points");
+  if (!d_points || !d_volume || !d_value || !d_valid) return invalid_arg(fn, "d_points, d_volume, d_value or d_valid is NULL");
+  if (points_frame_stride < 3 * n_points) return invalid_arg(fn, "points_frame_stride below 3 n_points");
   if (volume_frame_stride != 0 && volume_frame_stride < (long long)h->nx * h->ny * h->nz)
-    return vol_invalid(fn, "volume_frame_stride is neither 0 (shared) nor >= nx ny nz");
-  if (n_points >= (1ll << 39) / n_frames) return vol_invalid(fn, "2^39 points or more in one call");
+    return invalid_arg(fn, "volume_frame_stride is neither 0 (shared) nor >= nx ny nz");
+  if (n_points >= (1ll << 39) / n_frames) return invalid_arg(fn, "2^39 points or more in one call");
   HIP_TRY(hipSetDevice(h->device));
   VolumeArgs a;
   a.nx = h->nx; a.ny = h->ny; a.nz = h->nz;
@@ -79,27 +74,27 @@ int bodyfit_volume_integrate_device(bodyfit_volume* h, const float* d_depth, lon
                                     void* stream) {
   using namespace bodyfit;
   const char* fn = "bodyfit_volume_integrate_device";
-  if (!h) return vol_invalid(fn, "handle is NULL");
-  if (n_frames < 0) return vol_invalid(fn, "negative n_frames");
-  if (height < 1 || width < 1) return vol_invalid(fn, "height or width below 1");
-  if ((long long)height * width >= (1ll << 31)) return vol_invalid(fn, "2^31 pixels or more");
-  if (depth_frame_stride < (long long)height * width) return vol_invalid(fn, "depth_frame_stride below height width");
+  if (!h) return invalid_arg(fn, "handle is NULL");
+  if (n_frames < 0) return invalid_arg(fn, "negative n_frames");
+  if (height < 1 || width < 1) return invalid_arg(fn, "height or width below 1");
+  if ((long long)height * width >= (1ll << 31)) return invalid_arg(fn, "2^31 pixels or more");
+  if (depth_frame_stride < (long long)height * width) return invalid_arg(fn, "depth_frame_stride below height width");
   const long long n_voxels = (long long)h->nx * h->ny * h->nz;
   if (volume_frame_stride != 0 && volume_frame_stride < n_voxels)
-    return vol_invalid(fn, "volume_frame_stride is neither 0 (one volume) nor >= nx ny nz");
-  if (!std::isfinite(trunc) || !(trunc > 0.0)) return vol_invalid(fn, "trunc must be finite and positive");
-  if (!std::isfinite(z_near) || z_near < 0.0) return vol_invalid(fn, "z_near must be finite and not negative");
-  if (!(max_weight > 0.0)) return vol_invalid(fn, "max_weight must be positive (+inf: no cap)");
-  if (!intr) return vol_invalid(fn, "intr is NULL");
+    return invalid_arg(fn, "volume_frame_stride is neither 0 (one volume) nor >= nx ny nz");
+  if (!std::isfinite(trunc) || !(trunc > 0.0)) return invalid_arg(fn, "trunc must be finite and positive");
+  if (!std::isfinite(z_near) || z_near < 0.0) return invalid_arg(fn, "z_near must be finite and not negative");
+  if (!(max_weight > 0.0)) return invalid_arg(fn, "max_weight must be positive (+inf: no cap)");
+  if (!intr) return invalid_arg(fn, "intr is NULL");
   for (int a = 0; a < 4; ++a)
-    if (!std::isfinite(intr[a])) return vol_invalid(fn, "the intrinsics must be finite");
-  if (intr[0] == 0.0 || intr[1] == 0.0) return vol_invalid(fn, "fx or fy is zero");
+    if (!std::isfinite(intr[a])) return invalid_arg(fn, "the intrinsics must be finite");
+  if (intr[0] == 0.0 || intr[1] == 0.0) return invalid_arg(fn, "fx or fy is zero");
   // what there is to do: every frame's volume, or the one volume when there is a frame to fuse or the empty state to write
   const long long n_volumes = volume_frame_stride != 0 ? n_frames : (n_frames > 0 || reset ? 1 : 0);
   if (n_volumes == 0) return BODYFIT_OK;
-  if (!d_tsdf || !d_weight || (n_frames > 0 && !d_depth)) return vol_invalid(fn, "d_depth, d_tsdf or d_weight is NULL");
+  if (!d_tsdf || !d_weight || (n_frames > 0 && !d_depth)) return invalid_arg(fn, "d_depth, d_tsdf or d_weight is NULL");
   const long long chunks = (n_voxels + 255) / 256;
-  if (chunks * n_volumes >= (1ll << 31)) return vol_invalid(fn, "2^31 workgroups or more in one call");
+  if (chunks * n_volumes >= (1ll << 31)) return invalid_arg(fn, "2^31 workgroups or more in one call");
   HIP_TRY(hipSetDevice(h->device));
   TsdfArgs a;
   a.nx = h->nx; a.ny = h->ny; a.nz = h->nz;

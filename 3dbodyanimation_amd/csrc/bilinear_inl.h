@@ -1,5 +1,5 @@
 // The bilinear patch of an interleaved image and its exact derivative: the ONE statement of it, used by the image sampler
-// (k_rs_sample, k_raster.hip) and by the texture lookup and its gradient (k_texture.hip).  f64 and unfused: every function
+// (k_rs_sample, k_raster_shade.hip) and by the texture lookup and its gradient (k_texture.hip).  f64 and unfused: every function
 // switches contraction off for its own body, so it does not matter where an includer puts its own pragma.  The definitions and
 // their error bounds: include/bodyfit.h (bodyfit_raster_sample_device).
 #pragma once

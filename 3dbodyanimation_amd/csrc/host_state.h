@@ -16,6 +16,8 @@ namespace bodyfit {
 
 // sets what bodyfit_last_error() returns on this thread (the string itself lives in api_core.hip) and hands the code back
 inline int fail(int code, const std::string& msg) { return bodyfit_internal_fail(code, msg.c_str()); }
+// an entry's rejection of its arguments: BODYFIT_ERR_INVALID with "<entry>: <what>"
+inline int invalid_arg(const char* fn, const char* what) { return fail(BODYFIT_ERR_INVALID, std::string(fn) + ": " + what); }
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \

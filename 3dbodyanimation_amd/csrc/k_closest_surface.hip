@@ -38,7 +38,7 @@
 // rows = faces — then one thread per (frame, vertex) adds its incident (face, corner) entries in ascending (face, corner) order
 // through the vertex -> corner CSR the handle built from the topology.  No float atomics; every order depends on the frame alone.
 // Rows VJP (k_cs_rows_vjp_faces, k_cs_rows_vjp_verts; bodyfit_surface_rows_vjp_device): the same two stages for rows that arrive with
-// their weights, coefficient and direction (the depth rows of k_raster.hip, any point-to-plane row), summed in f64.
+// their weights, coefficient and direction (the depth rows of k_raster_rows.hip, any point-to-plane row), summed in f64.
 #include <hip/hip_runtime.h>
 
 #include <cmath>

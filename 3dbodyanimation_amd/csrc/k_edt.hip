@@ -1,5 +1,6 @@
-// Exact Euclidean distance transform WITH THE NEAREST SEED (a feature transform) of a batch of masks
-// (bodyfit_raster_distance_device, include/bodyfit.h: the definition, the tie rule and why the integer division is exact).
+// Exact Euclidean distance transform WITH THE NEAREST SEED (a feature transform) of a batch of masks and face-id images, on the
+// raster handle's size and workspace (bodyfit_raster_distance_device, include/bodyfit.h: the definition, the tie rule and why the
+// integer division is exact).
 // Separable, linear in the pixels, integers only, no atomics, plain stores:
 //
 //   k_edt_rows   one wave per (frame, row).  The row's seeds become one 64-bit ballot per 64 columns, kept in LDS (a row of 16384
@@ -21,14 +22,25 @@
 // bytes per row of g and stack, so 160 KiB of LDS hold 12 columns, a fifth of one wave.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstddef>
 #include <cstdint>
 
+#include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
-#include "edt.h"
+#include "raster_handle.h"
+
+using namespace bodyfit;
 
 namespace {
+
+// ints of workspace per pixel of a group of frames: the column pass's envelope stack (the row pass's seed columns pass
+// through the dist2 image)
+constexpr int kEdtWorkspaceInts = 2;
+// pixels of the largest group of frames transformed by one pair of launches: 4 GiB of workspace (the serial chains of the
+// column pass want as many columns in flight as there are; one frame is at most 16384 x 16384 = 2^28)
+constexpr long long kEdtGroupPixels = 1ll << 29;
 
 constexpr int kRowWaves = 4;        // rows per workgroup of k_edt_rows
 constexpr int kMaxWords = 256;      // 64-column words of the widest row (16384)
@@ -178,10 +190,9 @@ __global__ __launch_bounds__(kColThreads) void k_edt_cols(int32_t* image, uint2*
   }
 }
 
-}  // namespace
-
-namespace bodyfit {
-
+// The two passes over n_frames frames of H x W (n_frames H W <= kEdtGroupPixels), on `stream`: no allocation, no
+// synchronisation, no atomics.  seed: u8 (kind 0, seed iff != 0) or int32 (kind 1, seed iff >= 0), seed_stride elements between
+// frames; workspace: kEdtWorkspaceInts ints per pixel, 8-byte aligned; dist2, nearest (may be NULL): dense [n_frames][H][W].
 void edt_launch(const void* seed, int kind, long long seed_stride, int n_frames, int invert, int W, int H, int32_t* workspace,
                 int32_t* dist2, int32_t* nearest, hipStream_t stream) {
   const long long n_rows = (long long)n_frames * H, n_cols = (long long)n_frames * W;
@@ -195,4 +206,31 @@ void edt_launch(const void* seed, int kind, long long seed_stride, int n_frames,
   BODYFIT_LAUNCH(k_edt_cols, cgrid, dim3(kColThreads), 0, stream, dist2, stack, W, H, n_cols, nearest);
 }
 
-}  // namespace bodyfit
+}  // namespace
+
+extern "C" {
+
+int bodyfit_raster_distance_device(bodyfit_raster* r, const void* d_seed, int seed_kind, long long seed_frame_stride,
+                                   int n_frames, int invert, int32_t* d_dist2, int32_t* d_nearest, void* stream) {
+  const char* fn = "bodyfit_raster_distance_device";
+  if (int rc = rs_check_handle(fn, r, n_frames)) return rc;
+  if (seed_kind != 0 && seed_kind != 1) return invalid_arg(fn, "seed_kind must be 0 (u8) or 1 (int32)");
+  if (n_frames == 0) return BODYFIT_OK;
+  if (!d_seed || !d_dist2) return invalid_arg(fn, "d_seed or d_dist2 is NULL");
+  const long long ppf = (long long)r->W * r->H;
+  if (seed_frame_stride < ppf) return invalid_arg(fn, "seed_frame_stride below H W");
+  HIP_TRY(hipSetDevice(r->device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // groups of frames that share the workspace one after the other on the stream: its size follows from (F, H, W) alone
+  const int group = (int)std::max(1ll, std::min<long long>(n_frames, kEdtGroupPixels / ppf));
+  if (int rc = rs_grow(&r->d_edt, &r->edtCap, (size_t)group * ppf * kEdtWorkspaceInts)) return rc;
+  const size_t elem = seed_kind == 0 ? 1 : 4;
+  for (int f0 = 0; f0 < n_frames; f0 += group)
+    edt_launch(static_cast<const char*>(d_seed) + (size_t)f0 * seed_frame_stride * elem, seed_kind, seed_frame_stride,
+               std::min(group, n_frames - f0), invert, r->W, r->H, r->d_edt, d_dist2 + (size_t)f0 * ppf,
+               d_nearest ? d_nearest + (size_t)f0 * ppf : nullptr, st);
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+}  // extern "C"

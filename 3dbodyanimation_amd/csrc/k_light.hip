@@ -24,14 +24,10 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include <string>
-#include <type_traits>
 
 #include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
-#include "host_state.h"
-#include "raster_view.h"
-
+#include "raster_handle.h"
 #include "surface_handle.h"
 
 #pragma clang fp contract(off)
@@ -260,50 +256,34 @@ void lt_layout(long long ppf, long long* P, long long* chunks) {
   *chunks = ppf > 0 ? (ppf + 256 * p - 1) / (256 * p) : 0;
 }
 
-int lt_invalid(const char* fn, const char* what) {
-  return bodyfit_internal_fail(BODYFIT_ERR_INVALID, (std::string(fn) + ": " + what).c_str());
-}
-
 // what the two entries check alike; *work: there are pixels to write
 int lt_check(const char* fn, const bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
              long long verts_frame_stride, const float* d_normals, long long normals_frame_stride, const float* d_albedo,
              int n_channels, const float* d_light, long long light_frame_stride, int n_frames, bool* work) {
   *work = false;
-  if (!r) return lt_invalid(fn, "handle is NULL");
-  if (n_frames < 0) return lt_invalid(fn, "negative n_frames");
-  if (n_channels < 1 || n_channels > 4) return lt_invalid(fn, "n_channels outside 1 .. 4");
+  if (int rc = rs_check_handle(fn, r, n_frames)) return rc;
+  if (int rc = rs_check_channels(fn, n_channels)) return rc;
   if (light_frame_stride != 0 && light_frame_stride < 9ll * n_channels)
-    return lt_invalid(fn, "a non-zero light_frame_stride below 9 n_channels");
+    return invalid_arg(fn, "a non-zero light_frame_stride below 9 n_channels");
   if (n_frames == 0) return BODYFIT_OK;
-  const RasterView V = raster_view(r);
-  if (!d_face || !d_bary || !d_albedo || !d_light) return lt_invalid(fn, "d_face, d_bary, d_albedo or d_light is NULL");
-  if (V.nF > 0 && (!d_verts || !d_normals)) return lt_invalid(fn, "d_verts or d_normals is NULL");
-  if (verts_frame_stride < 3ll * V.nV) return lt_invalid(fn, "verts_frame_stride below 3 n_verts");
-  if (normals_frame_stride < 3ll * V.nV) return lt_invalid(fn, "normals_frame_stride below 3 n_verts");
-  if ((long long)V.W * V.H * n_frames >= (1ll << 39)) return lt_invalid(fn, "2^39 pixels or more in one call");
+  if (!d_face || !d_bary || !d_albedo || !d_light) return invalid_arg(fn, "d_face, d_bary, d_albedo or d_light is NULL");
+  if (r->nF > 0 && (!d_verts || !d_normals)) return invalid_arg(fn, "d_verts or d_normals is NULL");
+  if (int rc = rs_check_verts_stride(fn, r, verts_frame_stride)) return rc;
+  if (normals_frame_stride < 3ll * r->nV) return invalid_arg(fn, "normals_frame_stride below 3 n_verts");
+  if (int rc = rs_check_pixels(fn, r, n_frames)) return rc;
   *work = true;
   return BODYFIT_OK;
 }
 
-LtArgs lt_args(const RasterView& V, const int32_t* d_face, const float* d_bary, const float* d_verts, long long verts_frame_stride,
+LtArgs lt_args(const bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts, long long verts_frame_stride,
                const float* d_normals, long long normals_frame_stride, const float* d_albedo, const float* d_light,
                long long light_frame_stride) {
   LtArgs A;
   A.face_img = d_face; A.bary = d_bary; A.verts = d_verts; A.verts_stride = verts_frame_stride;
-  A.normals = d_normals; A.normals_stride = normals_frame_stride; A.faces = V.d_faces; A.nF = V.nF;
+  A.normals = d_normals; A.normals_stride = normals_frame_stride; A.faces = r->d_faces; A.nF = r->nF;
   A.albedo = d_albedo; A.light = d_light; A.light_stride = light_frame_stride;
-  A.ppf = (long long)V.W * V.H; A.P = 1; A.chunks = (A.ppf + 255) / 256;
+  A.ppf = (long long)r->W * r->H; A.P = 1; A.chunks = (A.ppf + 255) / 256;
   return A;
-}
-
-template <typename Launch>
-void lt_dispatch(int C, Launch&& launch) {
-  switch (C) {
-    case 1: launch(std::integral_constant<int, 1>{}); break;
-    case 2: launch(std::integral_constant<int, 2>{}); break;
-    case 3: launch(std::integral_constant<int, 3>{}); break;
-    default: launch(std::integral_constant<int, 4>{}); break;
-  }
 }
 
 struct NormalVjpArgs {
@@ -399,14 +379,13 @@ int bodyfit_raster_light_device(bodyfit_raster* r, const int32_t* d_face, const 
                         d_light, light_frame_stride, n_frames, &work))
     return rc;
   if (!work) return BODYFIT_OK;
-  if (!d_image) return lt_invalid(fn, "d_image is NULL");
-  const RasterView V = raster_view(r);
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_image) return invalid_arg(fn, "d_image is NULL");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LtArgs A = lt_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_normals, normals_frame_stride, d_albedo, d_light,
+  const LtArgs A = lt_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_normals, normals_frame_stride, d_albedo, d_light,
                            light_frame_stride);
   const dim3 grid((unsigned)(A.chunks * n_frames));
-  lt_dispatch(n_channels, [&](auto c) {
+  rs_dispatch_channels(n_channels, [&](auto c) {
     BODYFIT_LAUNCH((k_lt_forward<decltype(c)::value>), grid, dim3(256), 0, st, A, d_image, d_normal, d_shading);
   });
   HIP_TRY(hipGetLastError());
@@ -417,8 +396,8 @@ int bodyfit_light_grad_layout(long long pixels_per_frame, int n_channels, int n_
                               long long* n_chunks, long long* workspace_doubles) {
   using namespace bodyfit;
   const char* fn = "bodyfit_light_grad_layout";
-  if (pixels_per_frame < 0 || n_frames < 0) return lt_invalid(fn, "a negative count");
-  if (n_channels < 1 || n_channels > 4) return lt_invalid(fn, "n_channels outside 1 .. 4");
+  if (pixels_per_frame < 0 || n_frames < 0) return invalid_arg(fn, "a negative count");
+  if (int rc = rs_check_channels(fn, n_channels)) return rc;
   long long P = 1, chunks = 0;
   lt_layout(pixels_per_frame, &P, &chunks);
   if (chunk_pixels) *chunk_pixels = 256 * P;
@@ -439,19 +418,18 @@ int bodyfit_raster_light_grad_device(bodyfit_raster* r, const int32_t* d_face, c
                         d_light, light_frame_stride, n_frames, &work))
     return rc;
   if (!work || (!d_grad_albedo && !d_grad_m && !d_grad_light)) return BODYFIT_OK;
-  if (!d_grad_image) return lt_invalid(fn, "d_grad_image is NULL");
-  if (d_grad_light && !d_workspace) return lt_invalid(fn, "d_grad_light without d_workspace");
-  const RasterView V = raster_view(r);
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_grad_image) return invalid_arg(fn, "d_grad_image is NULL");
+  if (d_grad_light && !d_workspace) return invalid_arg(fn, "d_grad_light without d_workspace");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  LtArgs A = lt_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_normals, normals_frame_stride, d_albedo, d_light,
+  LtArgs A = lt_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_normals, normals_frame_stride, d_albedo, d_light,
                      light_frame_stride);
   long long P = 1;
   lt_layout(A.ppf, &P, &A.chunks);
   A.P = (int)P;
   double* partial = d_grad_light ? d_workspace : nullptr;
   const dim3 grid((unsigned)(A.chunks * n_frames));
-  lt_dispatch(n_channels, [&](auto c) {
+  rs_dispatch_channels(n_channels, [&](auto c) {
     BODYFIT_LAUNCH((k_lt_grad<decltype(c)::value>), grid, dim3(256), 0, st, A, d_grad_image, d_grad_albedo, d_grad_m, partial);
   });
   if (d_grad_light)

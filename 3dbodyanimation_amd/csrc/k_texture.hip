@@ -24,17 +24,16 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include <string>
 #include <type_traits>
 
 #include "../../include/bodyfit.h"
 #include "bilinear_inl.h"
 #include "bodyfit_device.h"
-#include "host_state.h"
-#include "raster_view.h"
-#include "solver_view.h"
+#include "raster_handle.h"
 
 #pragma clang fp contract(off)
+
+using namespace bodyfit;
 
 namespace {
 
@@ -233,60 +232,46 @@ __global__ __launch_bounds__(256) void k_tx_fold(const unsigned long long* __res
   grad_tex[i] = r;
 }
 
-int tx_invalid(const char* fn, const char* what) {
-  return bodyfit_internal_fail(BODYFIT_ERR_INVALID, (std::string(fn) + ": " + what).c_str());
-}
-
 // what the two entries check alike; *work: there are pixels to write
 int tx_check(const char* fn, const bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
              long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces, int tex_kind, int n_channels,
              int tex_height, int tex_width, long long tex_frame_stride, int n_frames, bool* work) {
   *work = false;
-  if (!r) return tx_invalid(fn, "handle is NULL");
-  if (n_frames < 0) return tx_invalid(fn, "negative n_frames");
-  if (n_channels < 1 || n_channels > 4) return tx_invalid(fn, "n_channels outside 1 .. 4");
-  if (tex_kind != 0 && tex_kind != 1) return tx_invalid(fn, "tex_kind must be 0 (u8) or 1 (f32)");
+  if (int rc = rs_check_handle(fn, r, n_frames)) return rc;
+  if (int rc = rs_check_channels(fn, n_channels)) return rc;
+  if (tex_kind != 0 && tex_kind != 1) return invalid_arg(fn, "tex_kind must be 0 (u8) or 1 (f32)");
   if (tex_height < 1 || tex_width < 1 || tex_height > 16384 || tex_width > 16384)
-    return tx_invalid(fn, "texture size outside 1 .. 16384");
-  if (n_uv < 0) return tx_invalid(fn, "negative n_uv");
+    return invalid_arg(fn, "texture size outside 1 .. 16384");
+  if (n_uv < 0) return invalid_arg(fn, "negative n_uv");
   if (tex_frame_stride != 0 && tex_frame_stride < (long long)tex_height * tex_width * n_channels)
-    return tx_invalid(fn, "a non-zero tex_frame_stride below Ht Wt n_channels");
+    return invalid_arg(fn, "a non-zero tex_frame_stride below Ht Wt n_channels");
   if (n_frames == 0) return BODYFIT_OK;
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  if (!d_face || !d_bary) return tx_invalid(fn, "d_face or d_bary is NULL");
-  if (V.nF > 0 && (!d_verts || !d_uv_faces)) return tx_invalid(fn, "d_verts or d_uv_faces is NULL");
-  if (V.nF > 0 && n_uv > 0 && !d_uv) return tx_invalid(fn, "d_uv is NULL");
-  if (verts_frame_stride < 3ll * V.nV) return tx_invalid(fn, "verts_frame_stride below 3 n_verts");
-  if ((long long)V.W * V.H * n_frames >= (1ll << 39)) return tx_invalid(fn, "2^39 pixels or more in one call");
+  if (!d_face || !d_bary) return invalid_arg(fn, "d_face or d_bary is NULL");
+  if (r->nF > 0 && (!d_verts || !d_uv_faces)) return invalid_arg(fn, "d_verts or d_uv_faces is NULL");
+  if (r->nF > 0 && n_uv > 0 && !d_uv) return invalid_arg(fn, "d_uv is NULL");
+  if (int rc = rs_check_verts_stride(fn, r, verts_frame_stride)) return rc;
+  if (int rc = rs_check_pixels(fn, r, n_frames)) return rc;
   *work = true;
   return BODYFIT_OK;
 }
 
-TxArgs tx_args(const bodyfit::RasterView& V, const int32_t* d_face, const float* d_bary, const float* d_verts,
+TxArgs tx_args(const bodyfit_raster* r, const int32_t* d_face, const float* d_bary, const float* d_verts,
                long long verts_frame_stride, const float* d_uv, int n_uv, const int32_t* d_uv_faces, int tex_height, int tex_width,
                long long tex_frame_stride, int n_frames) {
   TxArgs A;
-  A.face_img = d_face; A.bary = d_bary; A.verts = d_verts; A.verts_stride = verts_frame_stride; A.faces = V.d_faces;
-  A.uv = d_uv; A.uv_faces = d_uv_faces; A.nF = V.nF; A.T = n_uv; A.Wt = tex_width; A.Ht = tex_height;
-  A.tex_stride = tex_frame_stride; A.ppf = (long long)V.W * V.H; A.total = A.ppf * n_frames;
+  A.face_img = d_face; A.bary = d_bary; A.verts = d_verts; A.verts_stride = verts_frame_stride; A.faces = r->d_faces;
+  A.uv = d_uv; A.uv_faces = d_uv_faces; A.nF = r->nF; A.T = n_uv; A.Wt = tex_width; A.Ht = tex_height;
+  A.tex_stride = tex_frame_stride; A.ppf = (long long)r->W * r->H; A.total = A.ppf * n_frames;
   return A;
 }
 
+// launch(channel count, a null pointer of the texel type): u8 or f32 texels by tex_kind
 template <typename Launch>
 void tx_dispatch(int tex_kind, int C, Launch&& launch) {
-#define TX_CASE(c)                                        \
-  case c:                                                 \
-    if (tex_kind == 0) launch(std::integral_constant<int, c>{}, (const uint8_t*)nullptr); \
-    else launch(std::integral_constant<int, c>{}, (const float*)nullptr);                 \
-    break;
-  switch (C) {
-    TX_CASE(1)
-    TX_CASE(2)
-    TX_CASE(3)
-    default:
-    TX_CASE(4)
-  }
-#undef TX_CASE
+  rs_dispatch_channels(C, [&](auto c) {
+    if (tex_kind == 0) launch(c, (const uint8_t*)nullptr);
+    else launch(c, (const float*)nullptr);
+  });
 }
 
 // ---- mipmaps: the pyramid, the lookup with a level of detail, its gradients (include/bodyfit.h, MIPMAPS OF THE TEXTURE LOOKUP) -------
@@ -582,12 +567,11 @@ __global__ __launch_bounds__(256) void k_txm_fold(const unsigned long long* __re
 // the arguments the mip entries add to tx_check's; n_levels > 1 needs the pyramid
 int txm_check(const char* fn, double fx, double fy, double cx, double cy, float lod_bias, int n_levels, long long total,
               int n_channels, const float* d_mip, long long tex_frame_stride, long long mip_frame_stride) {
-  if (!(fx > 0.0) || !(fy > 0.0) || !(fx - fx == 0.0) || !(fy - fy == 0.0) || !(cx - cx == 0.0) || !(cy - cy == 0.0))
-    return tx_invalid(fn, "fx or fy <= 0 or a non-finite intrinsic");
-  if (lod_bias != lod_bias) return tx_invalid(fn, "lod_bias is NaN");
-  if (n_levels > 1 && !d_mip) return tx_invalid(fn, "d_mip is NULL with more than one level");
+  if (!rs_intrinsics_ok(fx, fy, cx, cy)) return invalid_arg(fn, "fx or fy <= 0 or a non-finite intrinsic");      // (this entry's wording)
+  if (lod_bias != lod_bias) return invalid_arg(fn, "lod_bias is NaN");
+  if (n_levels > 1 && !d_mip) return invalid_arg(fn, "d_mip is NULL with more than one level");
   if (n_levels > 1 && tex_frame_stride != 0 && mip_frame_stride < total * n_channels)
-    return tx_invalid(fn, "mip_frame_stride below the layout's total");
+    return invalid_arg(fn, "mip_frame_stride below the layout's total");
   return BODYFIT_OK;
 }
 
@@ -616,12 +600,11 @@ int bodyfit_raster_texture_device(bodyfit_raster* r, const int32_t* d_face, cons
                         tex_height, tex_width, tex_frame_stride, n_frames, &work))
     return rc;
   if (!work) return BODYFIT_OK;
-  if (!d_image) return tx_invalid(fn, "d_image is NULL");
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  if (V.nF > 0 && !d_tex) return tx_invalid(fn, "d_tex is NULL");
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_image) return invalid_arg(fn, "d_image is NULL");
+  if (r->nF > 0 && !d_tex) return invalid_arg(fn, "d_tex is NULL");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+  const TxArgs A = tx_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
                            tex_frame_stride, n_frames);
   const float4 bg = background ? make_float4(background[0], background[1], background[2], background[3])
                                : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -646,32 +629,31 @@ int bodyfit_raster_texture_grad_device(bodyfit_raster* r, const int32_t* d_face,
                         tex_height, tex_width, tex_frame_stride, n_frames, &work))
     return rc;
   if (!work || (!d_grad_uv && !d_grad_tex)) return BODYFIT_OK;
-  if (!d_grad_image) return tx_invalid(fn, "d_grad_image is NULL");
-  if (d_grad_tex && !d_workspace) return tx_invalid(fn, "d_grad_tex without d_workspace");
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  if (V.nF > 0 && d_grad_uv && !d_tex) return tx_invalid(fn, "d_grad_uv without d_tex");
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_grad_image) return invalid_arg(fn, "d_grad_image is NULL");
+  if (d_grad_tex && !d_workspace) return invalid_arg(fn, "d_grad_tex without d_workspace");
+  if (r->nF > 0 && d_grad_uv && !d_tex) return invalid_arg(fn, "d_grad_uv without d_tex");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+  const TxArgs A = tx_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
                            tex_frame_stride, n_frames);
   int B = 0;      // the bit length of the pixel count: total < 2^B
   while ((A.total >> B) != 0) ++B;
   const long long n_tex = (long long)tex_height * tex_width * n_channels * (tex_frame_stride ? n_frames : 1);
   const long long n_grad = A.total * n_channels;
-  if (d_grad_tex && n_tex >= (1ll << 39)) return tx_invalid(fn, "2^39 texel elements or more in one call");
-  HIP_TRY(hipMemsetAsync(V.d_scratch, 0, sizeof(unsigned), st));
+  if (d_grad_tex && n_tex >= (1ll << 39)) return invalid_arg(fn, "2^39 texel elements or more in one call");
+  HIP_TRY(hipMemsetAsync(r->scratch_word(), 0, sizeof(unsigned), st));
   if (d_grad_tex) HIP_TRY(hipMemsetAsync(d_workspace, 0, (size_t)n_tex * sizeof(long long), st));
   const unsigned mblocks = (unsigned)std::min<long long>((n_grad + 255) / 256, 4096);
-  BODYFIT_LAUNCH(k_tx_gmax, dim3(mblocks), dim3(256), 0, st, d_grad_image, n_grad, V.d_scratch);
+  BODYFIT_LAUNCH(k_tx_gmax, dim3(mblocks), dim3(256), 0, st, d_grad_image, n_grad, r->scratch_word());
   const dim3 grid((unsigned)((A.total + 255) / 256));
   unsigned long long* sums = d_grad_tex ? reinterpret_cast<unsigned long long*>(d_workspace) : nullptr;
   tx_dispatch(tex_kind, n_channels, [&](auto c, auto* type) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(type)>>;
     BODYFIT_LAUNCH((k_tx_grad<decltype(c)::value, T>), grid, dim3(256), 0, st, A, static_cast<const T*>(d_tex), d_grad_image,
-                   V.d_scratch, B, d_grad_uv, sums);
+                   r->scratch_word(), B, d_grad_uv, sums);
   });
   if (d_grad_tex)
-    BODYFIT_LAUNCH(k_tx_fold, dim3((unsigned)((n_tex + 255) / 256)), dim3(256), 0, st, sums, n_tex, V.d_scratch, B, d_grad_tex);
+    BODYFIT_LAUNCH(k_tx_fold, dim3((unsigned)((n_tex + 255) / 256)), dim3(256), 0, st, sums, n_tex, r->scratch_word(), B, d_grad_tex);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }
@@ -680,8 +662,8 @@ int bodyfit_texture_mip_layout(int tex_height, int tex_width, int max_level, int
                                long long* offsets, long long* total) {
   const char* fn = "bodyfit_texture_mip_layout";
   if (tex_height < 1 || tex_width < 1 || tex_height > 16384 || tex_width > 16384)
-    return tx_invalid(fn, "texture size outside 1 .. 16384");
-  if (!n_levels) return tx_invalid(fn, "n_levels is NULL");
+    return invalid_arg(fn, "texture size outside 1 .. 16384");
+  if (!n_levels) return invalid_arg(fn, "n_levels is NULL");
   int Hl[BODYFIT_TX_MAX_LEVELS], Wl[BODYFIT_TX_MAX_LEVELS];
   long long off[BODYFIT_TX_MAX_LEVELS], tot = 0;
   const int n = txm_layout(tex_height, tex_width, max_level, Hl, Wl, off, &tot);
@@ -699,24 +681,23 @@ int bodyfit_raster_texture_mip_build_device(bodyfit_raster* r, const void* d_tex
                                             int tex_width, long long tex_frame_stride, int n_textures, int max_level, float* d_mip,
                                             long long mip_frame_stride, void* stream) {
   const char* fn = "bodyfit_raster_texture_mip_build_device";
-  if (!r) return tx_invalid(fn, "handle is NULL");
-  if (n_textures < 0) return tx_invalid(fn, "negative n_textures");
-  if (n_channels < 1 || n_channels > 4) return tx_invalid(fn, "n_channels outside 1 .. 4");
-  if (tex_kind != 0 && tex_kind != 1) return tx_invalid(fn, "tex_kind must be 0 (u8) or 1 (f32)");
+  if (!r) return invalid_arg(fn, "handle is NULL");
+  if (n_textures < 0) return invalid_arg(fn, "negative n_textures");
+  if (int rc = rs_check_channels(fn, n_channels)) return rc;
+  if (tex_kind != 0 && tex_kind != 1) return invalid_arg(fn, "tex_kind must be 0 (u8) or 1 (f32)");
   if (tex_height < 1 || tex_width < 1 || tex_height > 16384 || tex_width > 16384)
-    return tx_invalid(fn, "texture size outside 1 .. 16384");
+    return invalid_arg(fn, "texture size outside 1 .. 16384");
   TxMip M;
   long long total = 0;
   M.n_levels = txm_layout(tex_height, tex_width, max_level, M.Hl, M.Wl, M.off, &total);
   if (n_textures > 1 && tex_frame_stride < (long long)tex_height * tex_width * n_channels)
-    return tx_invalid(fn, "tex_frame_stride below Ht Wt n_channels");
+    return invalid_arg(fn, "tex_frame_stride below Ht Wt n_channels");
   if (n_textures > 1 && M.n_levels > 1 && mip_frame_stride < total * n_channels)
-    return tx_invalid(fn, "mip_frame_stride below the layout's total");
+    return invalid_arg(fn, "mip_frame_stride below the layout's total");
   if (n_textures == 0 || M.n_levels == 1) return BODYFIT_OK;
-  if (!d_tex || !d_mip) return tx_invalid(fn, "d_tex or d_mip is NULL");
-  if (total * n_channels * n_textures >= (1ll << 39)) return tx_invalid(fn, "2^39 pyramid elements or more in one call");
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_tex || !d_mip) return invalid_arg(fn, "d_tex or d_mip is NULL");
+  if (total * n_channels * n_textures >= (1ll << 39)) return invalid_arg(fn, "2^39 pyramid elements or more in one call");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int C = n_channels;
   for (int l = 1; l < M.n_levels; ++l) {
@@ -755,12 +736,11 @@ int bodyfit_raster_texture_mip_device(bodyfit_raster* r, const int32_t* d_face, 
   if (int rc = txm_check(fn, fx, fy, cx, cy, lod_bias, M.n_levels, total, n_channels, d_mip, tex_frame_stride, mip_frame_stride))
     return rc;
   if (!work) return BODYFIT_OK;
-  if (!d_image) return tx_invalid(fn, "d_image is NULL");
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  if (V.nF > 0 && !d_tex) return tx_invalid(fn, "d_tex is NULL");
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_image) return invalid_arg(fn, "d_image is NULL");
+  if (r->nF > 0 && !d_tex) return invalid_arg(fn, "d_tex is NULL");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+  const TxArgs A = tx_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
                            tex_frame_stride, n_frames);
   const float4 bg = background ? make_float4(background[0], background[1], background[2], background[3])
                                : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -794,13 +774,12 @@ int bodyfit_raster_texture_mip_grad_device(bodyfit_raster* r, const int32_t* d_f
                          mip_frame_stride))
     return rc;
   if (!work || (!d_grad_uv && !d_grad_tex)) return BODYFIT_OK;
-  if (!d_grad_image) return tx_invalid(fn, "d_grad_image is NULL");
-  if (d_grad_tex && !d_workspace) return tx_invalid(fn, "d_grad_tex without d_workspace");
-  const bodyfit::RasterView V = bodyfit::raster_view(r);
-  if (V.nF > 0 && d_grad_uv && !d_tex) return tx_invalid(fn, "d_grad_uv without d_tex");
-  HIP_TRY(hipSetDevice(V.device));
+  if (!d_grad_image) return invalid_arg(fn, "d_grad_image is NULL");
+  if (d_grad_tex && !d_workspace) return invalid_arg(fn, "d_grad_tex without d_workspace");
+  if (r->nF > 0 && d_grad_uv && !d_tex) return invalid_arg(fn, "d_grad_uv without d_tex");
+  HIP_TRY(hipSetDevice(r->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const TxArgs A = tx_args(V, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
+  const TxArgs A = tx_args(r, d_face, d_bary, d_verts, verts_frame_stride, d_uv, n_uv, d_uv_faces, tex_height, tex_width,
                            tex_frame_stride, n_frames);
   int B = 0;      // the bit length of the pixel count: total < 2^B
   while ((A.total >> B) != 0) ++B;
@@ -809,21 +788,21 @@ int bodyfit_raster_texture_mip_grad_device(bodyfit_raster* r, const int32_t* d_f
   const long long n_tex = (long long)tex_height * tex_width * n_channels * n_textures;
   const long long n_work = pyramid * n_channels * n_textures;
   const long long n_grad = A.total * n_channels;
-  if (d_grad_tex && n_work >= (1ll << 39)) return tx_invalid(fn, "2^39 pyramid elements or more in one call");
-  HIP_TRY(hipMemsetAsync(V.d_scratch, 0, sizeof(unsigned), st));
+  if (d_grad_tex && n_work >= (1ll << 39)) return invalid_arg(fn, "2^39 pyramid elements or more in one call");
+  HIP_TRY(hipMemsetAsync(r->scratch_word(), 0, sizeof(unsigned), st));
   if (d_grad_tex) HIP_TRY(hipMemsetAsync(d_workspace, 0, (size_t)n_work * sizeof(long long), st));
   const unsigned mblocks = (unsigned)std::min<long long>((n_grad + 255) / 256, 4096);
-  BODYFIT_LAUNCH(k_tx_gmax, dim3(mblocks), dim3(256), 0, st, d_grad_image, n_grad, V.d_scratch);
+  BODYFIT_LAUNCH(k_tx_gmax, dim3(mblocks), dim3(256), 0, st, d_grad_image, n_grad, r->scratch_word());
   const dim3 grid((unsigned)((A.total + 255) / 256));
   unsigned long long* sums = d_grad_tex ? reinterpret_cast<unsigned long long*>(d_workspace) : nullptr;
   tx_dispatch(tex_kind, n_channels, [&](auto c, auto* type) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(type)>>;
     BODYFIT_LAUNCH((k_txm_grad<decltype(c)::value, T>), grid, dim3(256), 0, st, A, M, static_cast<const T*>(d_tex), d_grad_image,
-                   V.d_scratch, B, pyramid, d_grad_uv, sums);
+                   r->scratch_word(), B, pyramid, d_grad_uv, sums);
   });
   if (d_grad_tex)
     BODYFIT_LAUNCH(k_txm_fold, dim3((unsigned)((n_tex + 255) / 256)), dim3(256), 0, st, sums, M, n_channels, pyramid, n_tex,
-                   V.d_scratch, B, d_grad_tex);
+                   r->scratch_word(), B, d_grad_tex);
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

@@ -6,7 +6,7 @@
     term = PhotometricTerm(video, intr, faces, trunc=30.0, owner=True)   # sum rho(|I(pi(v)) - colour_v|^2) over the visible vertices
 
 The dense signal between the keypoints and the outline is the image itself.  render_attributes is render_depth followed by
-bodyfit_raster_shade_device (k_raster.hip: per-vertex attributes interpolated with the perspective-correct weights), its
+bodyfit_raster_shade_device (k_raster_shade.hip: per-vertex attributes interpolated with the perspective-correct weights), its
 backward bodyfit_surface_rows_vjp_device over the pixels.  sample_images is bodyfit_raster_sample_device (one bilinear read per
 vertex and frame, u8 or f32 images, with the image gradient of the cell).  fuse_vertex_colours averages the samples of the frames
 that see a vertex, weighted by the cosine to the camera; PhotometricTerm holds such colours against the frames and is
@@ -16,7 +16,7 @@ differentiable in the vertices and in the colours.
     term = RenderedPhotometricTerm(video, intr, faces, trunc=30.0)       # sum rho(|antialias(render) - I|^2) over the pixels
 
 interior=True adds the middle of rasterize -> interpolate -> antialias: the same image, and in the backward one row per shaded
-pixel from bodyfit_raster_interp_rows_device (k_raster.hip: the object-space barycentrics of the pixel's ray in its face and the
+pixel from bodyfit_raster_interp_rows_device (k_raster_rows.hip: the object-space barycentrics of the pixel's ray in its face and the
 one direction that carries dL/dimage to the three corners) into bodyfit_surface_rows_vjp_device.  RenderedPhotometricTerm is
 PhotometricTerm at the pixels instead of the vertices: interior and coverage gradients of one render.
 """

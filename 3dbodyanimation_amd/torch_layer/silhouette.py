@@ -13,7 +13,7 @@ uncovered; the second half's gradient is summed by bodyfit_surface_rows_vjp_devi
     w = edge_weights(verts, faces, intr, (H, W))                         # [F, H, W, 2]: the blend's weights, no gradient
     term = CoverageTerm(mask, intr, faces)                               # sum (antialias(covered) - mask)^2, pixel^2
 
-Every render is piecewise constant in the vertices.  antialias is bodyfit_raster_edges_device (k_raster.hip: per pair of
+Every render is piecewise constant in the vertices.  antialias is bodyfit_raster_edges_device (k_raster_edges.hip: per pair of
 neighbouring pixels owned by different faces, a bounded walk to the nearer face's silhouette edge and the fraction of the segment
 between the two centres it cuts off) followed by bodyfit_raster_edge_blend_device; its backward is that blend transposed for the
 image and, for the vertices, bodyfit_raster_edge_rows_device into bodyfit_surface_rows_vjp_device.  Of antialias only coverage

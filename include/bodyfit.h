@@ -995,7 +995,7 @@ int bodyfit_raster_render_device(bodyfit_raster* r, const float* d_verts, long l
 int bodyfit_raster_visibility_device(bodyfit_raster* r, const int32_t* d_face, int n_frames,
                                      uint8_t* d_face_visible /* may be NULL */, uint8_t* d_vert_visible /* may be NULL */,
                                      void* stream);
-/* DEPTH ROWS: the projective depth residual's rows at the correspondence a render already holds (k_rs_depth_rows, k_raster.hip).
+/* DEPTH ROWS: the projective depth residual's rows at the correspondence a render already holds (k_rs_depth_rows, k_raster_rows.hip).
  * A row is a pixel of a frame; its face is what d_face_image (int32 [n_frames][H][W], as rendered by this handle's topology and
  * size; a value outside [0, n_faces) is empty) holds there.  d_pixel int32 [N]: the linear index i W + j inside the row's frame;
  * d_offset int32 [n_frames + 1]: the rows of frame f are offset[f] .. offset[f + 1] - 1 (offset[0] = 0, offset[n_frames] = N, the
@@ -1066,7 +1066,7 @@ int bodyfit_raster_depth_rows_device(bodyfit_raster* r, const float* d_verts, lo
                                      long long n_rows, int32_t* d_index, float* d_z /* may be NULL */,
                                      float* d_bary /* may be NULL */, float* d_dir /* may be NULL */, void* stream);
 /* INTERPOLATION ROWS: the gradient of vertex attributes interpolated over a face, and of the ray-plane depth, in the face's three
- * corners, at the correspondence a render already holds (k_rs_interp_rows, k_raster.hip).  What bodyfit_raster_shade_device lacks:
+ * corners, at the correspondence a render already holds (k_rs_interp_rows, k_raster_rows.hip).  What bodyfit_raster_shade_device lacks:
  * how a pixel's colour changes when its face moves under the fixed pixel ray.  Rows, d_face_image, d_pixel, d_offset and n_rows are
  * exactly those of bodyfit_raster_depth_rows_device.  d_attr f32 rows of n_channels floats per vertex, attr_frame_stride floats
  * between frames (0: shared by the frames, else >= n_channels n_verts), as in bodyfit_raster_shade_device; d_grad_image f32
@@ -1199,7 +1199,7 @@ int bodyfit_raster_interp_rows_indexed_device(bodyfit_raster* r, const float* d_
 int bodyfit_raster_distance_device(bodyfit_raster* r, const void* d_seed, int seed_kind, long long seed_frame_stride,
                                    int n_frames, int invert, int32_t* d_dist2, int32_t* d_nearest /* may be NULL */,
                                    void* stream);
-/* VERTEX ATTRIBUTES OVER A RENDER (k_rs_shade, k_raster.hip): per-vertex attributes (colours) interpolated over a face-id image,
+/* VERTEX ATTRIBUTES OVER A RENDER (k_rs_shade, k_raster_shade.hip): per-vertex attributes (colours) interpolated over a face-id image,
  * perspective-correct.  d_face int32 [n_frames][H][W] and d_bary f32 [n_frames][H][W][3]: a render of this handle's topology and
  * size, or hand-made images.  d_verts f32 [n_frames][n_verts][3], verts_frame_stride floats between frames (>= 3 n_verts); only
  * the z of the corners is read.  d_attr f32 rows of n_channels floats per vertex, n_channels in 1 .. 4; attr_frame_stride floats
@@ -1232,7 +1232,7 @@ int bodyfit_raster_shade_device(bodyfit_raster* r, const int32_t* d_face, const 
                                 long long verts_frame_stride, const float* d_attr, long long attr_frame_stride, int n_channels,
                                 int n_frames, const float* background /* host [4]; may be NULL */, float* d_image,
                                 float* d_weight /* may be NULL */, void* stream);
-/* IMAGE SAMPLES AT PROJECTED POINTS (k_rs_sample, k_raster.hip): a batch of images read bilinearly where the points of a cloud
+/* IMAGE SAMPLES AT PROJECTED POINTS (k_rs_sample, k_raster_shade.hip): a batch of images read bilinearly where the points of a cloud
  * project, with the image gradient there.  The topology is not used: a handle with n_faces = 0 samples images (of its size), as
  * it transforms masks.  d_points f32 [n_frames][n_points][3], points_frame_stride floats between frames (>= 3 n_points:
  * bodyfit_device_views.cloud is used in place); intrinsics in f64 (fx, fy > 0), z_near > 0.  d_image: image_kind 0 = u8, 1 = f32,
@@ -1595,7 +1595,7 @@ int bodyfit_raster_light_grad_device(bodyfit_raster* r, const int32_t* d_face, c
                                      int n_frames, const float* d_grad_image, float* d_grad_albedo /* may be NULL */,
                                      float* d_grad_m /* may be NULL */, float* d_grad_light /* may be NULL */,
                                      double* d_workspace /* may be NULL without d_grad_light */, void* stream);
-/* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster.hip): the coverage of a render as a smooth
+/* SILHOUETTE-EDGE ANTIALIASING (k_rs_edges, k_rs_edge_blend, k_rs_edge_rows, k_raster_edges.hip): the coverage of a render as a smooth
  * function of the vertices, after Laine et al., "Modular Primitives for High-Performance Differentiable Rendering" (2020).  Only
  * COVERAGE carries a gradient here: how an attribute interpolates inside a face as its corners move is not part of it.
  * The handle keeps, per (face, edge e = corners e, (e + 1) % 3), the lowest-id OTHER face of the topology that holds both vertex ids

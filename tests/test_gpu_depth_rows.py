@@ -1,4 +1,4 @@
-"""GPU: the depth rows (bodyfit_raster_depth_rows_device, k_raster.hip), the rows VJP (bodyfit_surface_rows_vjp_device,
+"""GPU: the depth rows (bodyfit_raster_depth_rows_device, k_raster_rows.hip), the rows VJP (bodyfit_surface_rows_vjp_device,
 k_closest_surface.hip), torch_layer.depth_at_pixels and DepthResidualTerm.
 
 The kernels are checked against the extended-precision reference of their contracts (depth_rows_ref.py) on EVERY row and every

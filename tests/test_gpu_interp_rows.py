@@ -1,4 +1,4 @@
-"""GPU: the interpolation rows (bodyfit_raster_interp_rows_device, k_raster.hip), their sum through the rows VJP,
+"""GPU: the interpolation rows (bodyfit_raster_interp_rows_device, k_raster_rows.hip), their sum through the rows VJP,
 torch_layer.render_attributes(interior=True) and RenderedPhotometricTerm.
 
 The kernel is checked against the extended-precision reference of its contract (interp_ref.py) on EVERY row; the layer against torch
