@@ -346,6 +346,12 @@ def load_library():
     lib.bodyfit_volume_integrate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                                     C.POINTER(C.c_double), C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
                                                     C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    lib.bodyfit_volume_surface_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
+    lib.bodyfit_volume_surface_count_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float,
+                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.bodyfit_volume_surface_emit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float,
+                                                       C.c_float, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1417,6 +1423,31 @@ class Volume:
                                                               int(n_frames), None if k is None else _d(k), d_pose_ptr, float(trunc),
                                                               float(z_near), float(max_weight), 1 if reset else 0, d_tsdf_ptr,
                                                               d_weight_ptr, int(volume_frame_stride), stream))
+
+    def surface_layout(self, n_volumes: int) -> int:
+        """bodyfit_volume_surface_layout: the bytes of the workspace that surface_count_device and surface_emit_device share"""
+        n = C.c_longlong()
+        _check(load_library().bodyfit_volume_surface_layout(self.h, int(n_volumes), C.byref(n)))
+        return int(n.value)
+
+    def surface_count_device(self, d_volume_ptr: int, d_weight_ptr: int | None, volume_frame_stride: int, n_volumes: int,
+                             iso: float, min_weight: float, d_workspace_ptr: int, d_offsets_ptr: int, stream: int | None = None):
+        """bodyfit_volume_surface_count_device: marching cubes of the n_volumes volumes [nz, ny, nx] f32 at the level iso (weight:
+        the same shape or None; a voxel below min_weight is unusable), first half: offsets i64 [2, n_volumes + 1], the exclusive
+        vertex offsets of the volumes, then their face offsets, the last of each the total.  Asynchronous on `stream`."""
+        _check(load_library().bodyfit_volume_surface_count_device(self.h, d_volume_ptr, d_weight_ptr, int(volume_frame_stride),
+                                                                  int(n_volumes), float(iso), float(min_weight), d_workspace_ptr,
+                                                                  d_offsets_ptr, stream))
+
+    def surface_emit_device(self, d_volume_ptr: int, d_weight_ptr: int | None, volume_frame_stride: int, n_volumes: int,
+                            iso: float, min_weight: float, d_workspace_ptr: int, d_offsets_ptr: int, vert_capacity: int,
+                            face_capacity: int, d_verts_ptr: int | None, d_faces_ptr: int | None, stream: int | None = None):
+        """bodyfit_volume_surface_emit_device: second half, with the inputs, the workspace and the offsets of the count: verts f32
+        [vert_capacity, 3] and faces int32 [face_capacity, 3] (indices local to a volume); nothing is stored past a capacity."""
+        _check(load_library().bodyfit_volume_surface_emit_device(self.h, d_volume_ptr, d_weight_ptr, int(volume_frame_stride),
+                                                                 int(n_volumes), float(iso), float(min_weight), d_workspace_ptr,
+                                                                 d_offsets_ptr, int(vert_capacity), int(face_capacity), d_verts_ptr,
+                                                                 d_faces_ptr, stream))
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,5 +1,6 @@
 // The C ABI of the signed-distance volumes (include/bodyfit.h: bodyfit_volume_create / _destroy / _sample_device /
-// _integrate_device): the handle, the argument checks and the one launch of each call (k_volume.hip, k_tsdf.hip through volume.h).
+// _integrate_device / _surface_layout / _surface_count_device / _surface_emit_device): the handle, the argument checks and the
+// launches of each call (k_volume.hip, k_tsdf.hip, k_surface_extract.hip through volume.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,6 +16,51 @@ struct bodyfit_volume {
 };
 
 using bodyfit::invalid_arg;
+
+namespace {
+
+// The checks that the two surface entries share, and the kernels' arguments but for the outputs.  *work: 1 when there is something
+// to launch, 0 for the no-ops (no volumes, or an axis of length 1: no cells).
+int surface_args(const char* fn, bodyfit_volume* h, const float* d_volume, const float* d_weight, long long volume_frame_stride,
+                 int n_volumes, float iso, float min_weight, void* d_workspace, long long* d_offsets, bodyfit::SurfaceArgs* a,
+                 int* work) {
+  *work = 0;
+  if (!h) return invalid_arg(fn, "handle is NULL");
+  if (n_volumes < 0) return invalid_arg(fn, "negative n_volumes");
+  const long long n_voxels = (long long)h->nx * h->ny * h->nz;
+  if (volume_frame_stride != 0 && volume_frame_stride < n_voxels)
+    return invalid_arg(fn, "volume_frame_stride is neither 0 nor >= nx ny nz");
+  if (!std::isfinite(iso)) return invalid_arg(fn, "iso must be finite");
+  if (std::isnan(min_weight)) return invalid_arg(fn, "min_weight is NaN");
+  // at most three vertices per voxel and five triangles per cell: below 2^31 of either in one volume
+  const long long n_cells = (long long)(h->nx - 1) * (h->ny - 1) * (h->nz - 1);
+  if (3 * n_voxels >= (1ll << 31) || 5 * n_cells >= (1ll << 31))
+    return invalid_arg(fn, "a volume that could hold 2^31 vertices or faces or more (3 nx ny nz, 5 cells)");
+  if (n_volumes == 0) return BODYFIT_OK;
+  if (!d_offsets) return invalid_arg(fn, "d_offsets is NULL");
+  if (n_cells == 0) return BODYFIT_OK;
+  if (!d_volume || !d_workspace) return invalid_arg(fn, "d_volume or d_workspace is NULL");
+  const long long chunks = (n_voxels + 255) / 256;
+  if (chunks * n_volumes >= (1ll << 31)) return invalid_arg(fn, "2^31 workgroups or more in one call");
+  a->nx = h->nx; a->ny = h->ny; a->nz = h->nz;
+  a->n_voxels = (unsigned)n_voxels; a->chunks = (unsigned)chunks; a->F = n_volumes;
+  a->iso = iso; a->min_weight = min_weight;
+  a->volume = d_volume; a->weight = d_weight; a->volume_stride = volume_frame_stride;
+  for (int k = 0; k < 3; ++k) { a->origin[k] = h->origin[k]; a->spacing[k] = h->spacing[k]; }
+  const bodyfit::SurfaceWorkspace w = bodyfit::surface_workspace(n_voxels, n_volumes);
+  char* base = static_cast<char*>(d_workspace);
+  a->code = reinterpret_cast<unsigned char*>(base + w.code);
+  a->word = reinterpret_cast<unsigned short*>(base + w.word);
+  a->block_verts = reinterpret_cast<unsigned*>(base + w.block_verts);
+  a->block_tris = reinterpret_cast<unsigned*>(base + w.block_tris);
+  a->totals = reinterpret_cast<unsigned*>(base + w.totals);
+  a->offsets = d_offsets;
+  a->vert_capacity = a->face_capacity = 0; a->verts = nullptr; a->faces = nullptr;
+  *work = 1;
+  return BODYFIT_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -106,6 +152,61 @@ int bodyfit_volume_integrate_device(bodyfit_volume* h, const float* d_depth, lon
   a.trunc = trunc; a.z_near = z_near; a.max_weight = max_weight; a.reset = reset;
   a.tsdf = d_tsdf; a.weight = d_weight; a.volume_stride = volume_frame_stride;
   launch_tsdf_integrate(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_surface_layout(bodyfit_volume* h, int n_volumes, long long* workspace_bytes) {
+  const char* fn = "bodyfit_volume_surface_layout";
+  if (!h) return invalid_arg(fn, "handle is NULL");
+  if (!workspace_bytes) return invalid_arg(fn, "workspace_bytes is NULL");
+  if (n_volumes < 0) return invalid_arg(fn, "negative n_volumes");
+  *workspace_bytes = bodyfit::surface_workspace((long long)h->nx * h->ny * h->nz, n_volumes).bytes;
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_surface_count_device(bodyfit_volume* h, const float* d_volume, const float* d_weight, long long volume_frame_stride,
+                                        int n_volumes, float iso, float min_weight, void* d_workspace, long long* d_offsets,
+                                        void* stream) {
+  using namespace bodyfit;
+  SurfaceArgs a;
+  int work = 0;
+  const int rc = surface_args("bodyfit_volume_surface_count_device", h, d_volume, d_weight, volume_frame_stride, n_volumes, iso,
+                              min_weight, d_workspace, d_offsets, &a, &work);
+  if (rc != BODYFIT_OK) return rc;
+  if (!work) {
+    // no volumes, or no cells: the offsets are all zero (with no volumes and no d_offsets there is nothing to write)
+    if (d_offsets) {
+      HIP_TRY(hipSetDevice(h->device));
+      HIP_TRY(hipMemsetAsync(d_offsets, 0, 2 * ((size_t)n_volumes + 1) * sizeof(long long), static_cast<hipStream_t>(stream)));
+    }
+    return BODYFIT_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  launch_surface_count(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_surface_emit_device(bodyfit_volume* h, const float* d_volume, const float* d_weight, long long volume_frame_stride,
+                                       int n_volumes, float iso, float min_weight, void* d_workspace, const long long* d_offsets,
+                                       long long vert_capacity, long long face_capacity, float* d_verts, int32_t* d_faces,
+                                       void* stream) {
+  using namespace bodyfit;
+  const char* fn = "bodyfit_volume_surface_emit_device";
+  SurfaceArgs a;
+  int work = 0;
+  const int rc = surface_args(fn, h, d_volume, d_weight, volume_frame_stride, n_volumes, iso, min_weight, d_workspace,
+                              const_cast<long long*>(d_offsets), &a, &work);
+  if (rc != BODYFIT_OK) return rc;
+  if (vert_capacity < 0 || face_capacity < 0) return invalid_arg(fn, "negative vert_capacity or face_capacity");
+  if (!work) return BODYFIT_OK;
+  if ((vert_capacity > 0 && !d_verts) || (face_capacity > 0 && !d_faces))
+    return invalid_arg(fn, "d_verts or d_faces is NULL with a capacity above 0");
+  if (vert_capacity == 0 && face_capacity == 0) return BODYFIT_OK;
+  a.vert_capacity = vert_capacity; a.face_capacity = face_capacity; a.verts = d_verts; a.faces = d_faces;
+  HIP_TRY(hipSetDevice(h->device));
+  launch_surface_emit(a, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

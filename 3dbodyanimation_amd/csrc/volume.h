@@ -1,5 +1,5 @@
-// volume.h — what api_volume.hip (the host side of bodyfit_volume_sample_device and bodyfit_volume_integrate_device) launches from
-// k_volume.hip and k_tsdf.hip.
+// volume.h — what api_volume.hip (the host side of bodyfit_volume_sample_device, bodyfit_volume_integrate_device and
+// bodyfit_volume_surface_*) launches from k_volume.hip, k_tsdf.hip and k_surface_extract.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,5 +41,48 @@ struct TsdfArgs {
 
 // one launch of k_tsdf_integrate over the voxels of the one volume (a.volume_stride == 0, a.F >= 0) or of the a.F > 0 volumes, on `st`
 void launch_tsdf_integrate(const TsdfArgs& a, hipStream_t st);
+
+
+struct SurfaceArgs {
+  int nx, ny, nz;
+  unsigned n_voxels, chunks;      // nx ny nz < 2^31 / 3; workgroups per volume: ceil(n_voxels / 256); chunks F < 2^31
+  int F;                          // volumes
+  float iso, min_weight;
+  const float* volume;            // [nz][ny][nx], volume_stride elements between the volumes
+  const float* weight;            // the same shape, or null
+  long long volume_stride;
+  double origin[3], spacing[3];
+  // the workspace (surface_workspace: bodyfit_volume_surface_layout)
+  unsigned char* code;            // [F][n_voxels]: the cell whose corner 0 the voxel is: its case, 0 when dead or not a cell
+  unsigned short* word;           // [F][n_voxels]: edge flags x, y, z << 13 | the exclusive vertex offset inside the workgroup
+  unsigned* block_verts;          // [F][chunks]: a workgroup's vertices; after k_mc_scan: exclusive inside the volume
+  unsigned* block_tris;           // [F][chunks]: a workgroup's triangles, alike
+  unsigned* totals;               // [F][2]: a volume's vertices and triangles
+  long long* offsets;             // the caller's [2][F + 1]
+  // k_mc_emit only
+  long long vert_capacity, face_capacity;
+  float* verts;                   // [.][3]
+  int* faces;                     // [.][3]
+};
+
+// the byte offsets of the workspace's arrays for F volumes of n_voxels voxels, and its size
+struct SurfaceWorkspace { long long code, word, block_verts, block_tris, totals, bytes; };
+inline SurfaceWorkspace surface_workspace(long long n_voxels, long long F) {
+  const long long chunks = (n_voxels + 255) / 256;
+  auto up = [](long long b) { return (b + 255) / 256 * 256; };
+  SurfaceWorkspace w;
+  w.code = 0;
+  w.word = w.code + up(F * n_voxels);
+  w.block_verts = w.word + up(2 * F * n_voxels);
+  w.block_tris = w.block_verts + up(4 * F * chunks);
+  w.totals = w.block_tris + up(4 * F * chunks);
+  w.bytes = w.totals + up(8 * F);
+  return w;
+}
+
+// bodyfit_volume_surface_count_device: k_mc_classify, k_mc_count, k_mc_scan and k_mc_offsets over the a.F > 0 volumes, on `st`
+void launch_surface_count(const SurfaceArgs& a, hipStream_t st);
+// bodyfit_volume_surface_emit_device: k_mc_emit
+void launch_surface_emit(const SurfaceArgs& a, hipStream_t st);
 
 }  // namespace bodyfit

@@ -1802,11 +1802,79 @@ int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long 
  * < 0; max_weight not > 0 (+inf: no cap); NULL intr, an intrinsic that is not finite, fx or fy zero; with work to do: NULL
  * d_tsdf / d_weight, NULL d_depth with frames to fuse, 2^31 workgroups (256 voxels each, per volume) or more.
  * NOT BUILT: the Euclidean ray length as the measure, a bilinear depth lookup, per-pixel weights, colour volumes, the gradient
- * in the voxels, surface extraction, and the entry of the C++ mirror header.                                                   */
+ * in the voxels, and the entry of the C++ mirror header.                                                                       */
 int bodyfit_volume_integrate_device(bodyfit_volume* h, const float* d_depth, long long depth_frame_stride, int height, int width,
                                     int n_frames, const double intr[4], const double* d_pose /* [n_frames][12] or NULL */,
                                     double trunc, double z_near, double max_weight, int reset, float* d_tsdf, float* d_weight,
                                     long long volume_frame_stride, void* stream);
+/* SURFACE EXTRACTION (k_mc_*, k_surface_extract.hip): the level set value = iso of a volume of the handle's geometry as a welded
+ * triangle mesh, marching cubes: what turns a fused TSDF or a voxelised scene back into the vertices and faces that the mesh
+ * entries take (bodyfit_raster_render_device, bodyfit_surface_*).  d_volume f32 [nz][ny][nx], or n_volumes of them
+ * volume_frame_stride ELEMENTS apart (>= nx ny nz; or 0, the sampler's shared volume: every one of the n_volumes is the same);
+ * d_weight the same shape and stride, or NULL.
+ * DEFINITION.  A voxel is USABLE iff its value is finite and (d_weight is NULL or its weight >= min_weight: false on a NaN
+ * weight).  It is INSIDE iff value < iso, compared exactly on the f32 values: -0.0 and a value equal to iso are outside.  A CELL
+ * (k, j, i), 0 <= i <= nx - 2 and alike in j and k (an axis of length 1 has no cells: the result is empty), has the corners
+ * c = 0 .. 7 at (i + (c & 1), j + (c >> 1 & 1), k + (c >> 2 & 1)); it is LIVE iff all eight are usable (the sampler's rule for a
+ * dead cell), and its CASE is the 8-bit number whose bit c is set iff corner c is inside.
+ * THE TABLE (csrc/mc_table_inl.h, WRITTEN BY tools/gen_mc_table.py from this rule; it is part of the definition).  Cube edge
+ * e = 4 axis + r joins the r-th corner (ascending) whose `axis` bit is clear to that corner with the bit set: axis 0: (0,1) (2,3)
+ * (4,5) (6,7); axis 1: (0,2) (1,3) (4,6) (5,7); axis 2: (0,4) (1,5) (2,6) (3,7).  On each of the six cube faces the crossed face
+ * edges are joined by segments: two crossings, one segment; four crossings (the ambiguous face), two segments that each cut off ONE
+ * INSIDE corner, so inside corners are separated; the two cells that share a face see the same four signs and draw the same
+ * segments.  Every segment is directed with one handedness (seen from outside the cube, the inside corners it cuts off lie on its
+ * right), which makes case 1 (corner 0 alone inside) the triangle (0, 4, 8), its normal away from corner 0: normals point towards
+ * INCREASING values, outward for a voxelised mesh (negative inside), towards the sensor for a TSDF.  A crossed edge lies on two
+ * faces and so has one segment in and one out: following them closes loops, taken in ascending order of their smallest edge, each
+ * from that edge in its direction.  A loop of length L gives the fan of L - 2 triangles (a, v_m, v_m+1), m = 1 .. L - 2, from an
+ * apex a = v_0: the first rotation of the loop none of whose fan diagonals (a, v_m), 2 <= m <= L - 2, joins two edges of one cube
+ * face: such a diagonal would lie in that face and coincide with a diagonal or a segment of the neighbouring cell there, an edge
+ * used by more than two triangles.  (Derived, not recalled: every case has an apex; 820 triangles in all, at most 5 in a row,
+ * 2 / 16 / 50 / 80 / 76 / 32 rows with 0 .. 5; because the segments on a shared face agree and are traversed in opposite
+ * directions by the two cells, every interior triangle edge is used once in each direction: the mesh is a closed oriented manifold
+ * wherever no dead cell and no border of the volume cuts it.  tests/test_extract.py checks all of it.)
+ * VERTICES (welded).  Voxel (k, j, i) OWNS the three grid edges that leave it towards +x, +y, +z.  An owned edge carries a vertex
+ * iff both ends are usable, exactly one end is inside AND at least one of the up to four cells around the edge is live: no vertex
+ * is unreferenced.  Order: ascending linear index (k ny + j) nx + i of the owner, then x, y, z within an owner.  Position, with a
+ * the owner, b the neighbour and t = (iso - V_a) / (V_b - V_a) (0 <= t <= 1): origin + (index + t) spacing along the edge, origin
+ * + index spacing on the other two axes.
+ * FACES.  A live cell emits its case's triangles in table order, the cells in ascending linear index of their corner 0; a corner is
+ * the index of the vertex on that cube edge, int32, LOCAL to its volume.  Zero-area triangles (a value equal to iso: t = 0) are
+ * kept: the topology stays manifold, and bodyfit_surface_closest_device defines degenerate faces.
+ * bodyfit_volume_surface_layout: the bytes of the workspace that the two device entries share for n_volumes volumes (3 bytes per
+ * voxel and 8 per 256 voxels, rounded up).  bodyfit_volume_surface_count_device: d_offsets i64 [2][n_volumes + 1], the exclusive
+ * vertex offsets of the volumes, then their face offsets; the last of each is the total.  bodyfit_volume_surface_emit_device, with
+ * THE SAME inputs, workspace and offsets (the caller reads the totals, allocates and must not change the volume in between; emit
+ * reads the volume again for the positions): d_verts f32 [vert_capacity][3], volume f's at offsets[0][f]; d_faces i32
+ * [face_capacity][3], volume f's at offsets[1][f].  EVERY STORE IS GUARDED by the capacities: a caller that passes less than the
+ * totals gets the leading part of the mesh and no write past its buffers.
+ * CONTRACT, with u = 2^-24 and eps = 2^-53: the offsets, the totals and every face index are EXACT.  The coordinate along the edge
+ * satisfies |x^ - x*| <= u |x*| + 2^-50 (|origin_a| + (index + 1) s_a) + 2^-149; the other two are within u |x*| + 2^-51
+ * (|origin_a| + index s_a) + 2^-149.  Derivation (every operation f64 and unfused, one store to f32): an f32 value is exact in
+ * f64; iso - V_a, V_b - V_a and their quotient round once each, and rounding is monotone, so t^ stays in [0, 1] and |t^ - t| <=
+ * 3.01 eps; index + t^ rounds once, eps (index + 1); the product with s_a once, eps (index + 1) s_a; the sum with the origin once,
+ * eps (|origin_a| + (index + 1) s_a): together below 6.1 eps (|origin_a| + (index + 1) s_a) < 2^-50 (...).  Off the edge: a product
+ * and a sum, 2 eps (...) = 2^-52 (...), stated as 2^-51.  The store rounds once, u |x*|, to a multiple of 2^-149 below 2^-126.
+ * Five launches: per voxel a byte (its cell's case, 0 when dead) and a u16 (its edge flags over its vertex offset inside the
+ * workgroup), a scan of the workgroup sums per volume, a scan over the volumes, the emit.  Integer sums in a fixed order, plain
+ * stores, no atomics: bit-identical from run to run, and a volume's mesh is bit-identical whatever n_volumes and its place in the
+ * batch.  Asynchronous on `stream`; no host synchronisation, no allocation; the handle still owns no device memory.
+ * n_volumes == 0: nothing is launched and the two zero offsets are written (when d_offsets is given); an axis of length 1: nothing
+ * is launched and the offsets are zeroed.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle; n_volumes < 0; a volume stride
+ * that is neither 0 nor >= nx ny nz; iso not finite; min_weight NaN; a geometry that could hold 2^31 vertices or faces of one volume
+ * or more (3 nx ny nz or 5 (nx - 1)(ny - 1)(nz - 1) >= 2^31); with volumes: NULL d_offsets, and with cells: NULL d_volume or
+ * d_workspace, 2^31 workgroups (256 voxels each, per volume) or more; emit: a negative capacity, NULL d_verts or d_faces with a
+ * capacity above 0 (both capacities 0: a successful no-op).
+ * NOT BUILT: vertex normals or colours from the volume, the gradient of the vertices in the voxels, decimation, a capacity-only
+ * single call without the host's read of the totals, and the entries of the C++ mirror header.                                 */
+int bodyfit_volume_surface_layout(bodyfit_volume* h, int n_volumes, long long* workspace_bytes);
+int bodyfit_volume_surface_count_device(bodyfit_volume* h, const float* d_volume, const float* d_weight /* may be NULL */,
+                                        long long volume_frame_stride, int n_volumes, float iso, float min_weight,
+                                        void* d_workspace, long long* d_offsets /* i64 [2][n_volumes + 1] */, void* stream);
+int bodyfit_volume_surface_emit_device(bodyfit_volume* h, const float* d_volume, const float* d_weight /* may be NULL */,
+                                       long long volume_frame_stride, int n_volumes, float iso, float min_weight,
+                                       void* d_workspace, const long long* d_offsets, long long vert_capacity,
+                                       long long face_capacity, float* d_verts, int32_t* d_faces, void* stream);
 
 /* kernels launched by this process through the library so far (benchmarks: launches per LM iteration) */
 long bodyfit_launch_count(void);
