@@ -352,6 +352,9 @@ def load_library():
     lib.bodyfit_volume_surface_emit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float,
                                                        C.c_float, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p,
                                                        C.c_void_p, C.c_void_p]
+    lib.bodyfit_volume_distance_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
+    lib.bodyfit_volume_distance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -1448,6 +1451,22 @@ class Volume:
                                                                  int(n_volumes), float(iso), float(min_weight), d_workspace_ptr,
                                                                  d_offsets_ptr, int(vert_capacity), int(face_capacity), d_verts_ptr,
                                                                  d_faces_ptr, stream))
+
+    def distance_layout(self, n_volumes: int) -> int:
+        """bodyfit_volume_distance_layout: the bytes of distance_device's workspace for n_volumes volumes"""
+        n = C.c_longlong()
+        _check(load_library().bodyfit_volume_distance_layout(self.h, int(n_volumes), C.byref(n)))
+        return int(n.value)
+
+    def distance_device(self, d_seed_ptr: int, seed_kind: int, seed_volume_stride: int, n_volumes: int, invert: bool,
+                        d_workspace_ptr: int, d_dist2_ptr: int, d_nearest_ptr: int | None = None, stream: int | None = None):
+        """bodyfit_volume_distance_device: the exact squared Euclidean distance dist2 [n_volumes, nz, ny, nx] int32, in index
+        units, of every voxel to the nearest seed of its volume and, unless None, nearest = (k' ny + j') nx + i' of a seed that
+        attains it (INT32_MAX / -1 in a volume without a seed).  seed_kind 0: u8, a seed iff != 0; 1: int32, a seed iff >= 0;
+        invert swaps seeds and non-seeds.  Asynchronous on `stream`, no host synchronisation."""
+        _check(load_library().bodyfit_volume_distance_device(self.h, d_seed_ptr, int(seed_kind), int(seed_volume_stride),
+                                                             int(n_volumes), 1 if invert else 0, d_workspace_ptr, d_dist2_ptr,
+                                                             d_nearest_ptr, stream))
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,9 +1,12 @@
 // The C ABI of the signed-distance volumes (include/bodyfit.h: bodyfit_volume_create / _destroy / _sample_device /
-// _integrate_device / _surface_layout / _surface_count_device / _surface_emit_device): the handle, the argument checks and the
-// launches of each call (k_volume.hip, k_tsdf.hip, k_surface_extract.hip through volume.h).
+// _integrate_device / _surface_layout / _surface_count_device / _surface_emit_device / _distance_layout / _distance_device): the
+// handle, the argument checks and the launches of each call (k_volume.hip, k_tsdf.hip, k_surface_extract.hip, k_edt3.hip through
+// volume.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 
 #include "../../include/bodyfit.h"
 #include "host_state.h"
@@ -57,6 +60,15 @@ int surface_args(const char* fn, bodyfit_volume* h, const float* d_volume, const
   a->offsets = d_offsets;
   a->vert_capacity = a->face_capacity = 0; a->verts = nullptr; a->faces = nullptr;
   *work = 1;
+  return BODYFIT_OK;
+}
+
+// the checks that the two distance entries share
+int distance_handle(const char* fn, bodyfit_volume* h, int n_volumes) {
+  if (!h) return invalid_arg(fn, "handle is NULL");
+  if (n_volumes < 0) return invalid_arg(fn, "negative n_volumes");
+  if (std::max(h->nx, std::max(h->ny, h->nz)) > bodyfit::kDistanceMaxDim)
+    return invalid_arg(fn, "a dimension above 16384 (the int32 range of the transform)");
   return BODYFIT_OK;
 }
 
@@ -207,6 +219,34 @@ int bodyfit_volume_surface_emit_device(bodyfit_volume* h, const float* d_volume,
   a.vert_capacity = vert_capacity; a.face_capacity = face_capacity; a.verts = d_verts; a.faces = d_faces;
   HIP_TRY(hipSetDevice(h->device));
   launch_surface_emit(a, static_cast<hipStream_t>(stream));
+  HIP_TRY(hipGetLastError());
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_distance_layout(bodyfit_volume* h, int n_volumes, long long* workspace_bytes) {
+  const char* fn = "bodyfit_volume_distance_layout";
+  if (int rc = distance_handle(fn, h, n_volumes)) return rc;
+  if (!workspace_bytes) return invalid_arg(fn, "workspace_bytes is NULL");
+  *workspace_bytes = bodyfit::distance_workspace((long long)h->nx * h->ny * h->nz, n_volumes).bytes;
+  return BODYFIT_OK;
+}
+
+int bodyfit_volume_distance_device(bodyfit_volume* h, const void* d_seed, int seed_kind, long long seed_volume_stride, int n_volumes,
+                                   int invert, void* d_workspace, int32_t* d_dist2, int32_t* d_nearest, void* stream) {
+  using namespace bodyfit;
+  const char* fn = "bodyfit_volume_distance_device";
+  if (int rc = distance_handle(fn, h, n_volumes)) return rc;
+  if (seed_kind != 0 && seed_kind != 1) return invalid_arg(fn, "seed_kind must be 0 (u8) or 1 (int32)");
+  if (n_volumes == 0) return BODYFIT_OK;
+  if (!d_seed || !d_dist2 || !d_workspace) return invalid_arg(fn, "d_seed, d_dist2 or d_workspace is NULL");
+  if (reinterpret_cast<uintptr_t>(d_workspace) % 8 != 0) return invalid_arg(fn, "d_workspace is not 8-byte aligned");
+  if (seed_volume_stride < (long long)h->nx * h->ny * h->nz) return invalid_arg(fn, "seed_volume_stride below nx ny nz");
+  HIP_TRY(hipSetDevice(h->device));
+  DistanceArgs a;
+  a.nx = h->nx; a.ny = h->ny; a.nz = h->nz; a.F = n_volumes;
+  a.seed = d_seed; a.kind = seed_kind; a.invert = invert; a.seed_stride = seed_volume_stride;
+  a.workspace = d_workspace; a.dist2 = d_dist2; a.nearest = d_nearest;
+  launch_volume_distance(a, static_cast<hipStream_t>(stream));
   HIP_TRY(hipGetLastError());
   return BODYFIT_OK;
 }

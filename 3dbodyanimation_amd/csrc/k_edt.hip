@@ -29,15 +29,13 @@
 
 #include "../../include/bodyfit.h"
 #include "bodyfit_device.h"
+#include "edt.h"
 #include "raster_handle.h"
 
 using namespace bodyfit;
 
 namespace {
 
-// ints of workspace per pixel of a group of frames: the column pass's envelope stack (the row pass's seed columns pass
-// through the dist2 image)
-constexpr int kEdtWorkspaceInts = 2;
 // pixels of the largest group of frames transformed by one pair of launches: 4 GiB of workspace (the serial chains of the
 // column pass want as many columns in flight as there are; one frame is at most 16384 x 16384 = 2^28)
 constexpr long long kEdtGroupPixels = 1ll << 29;
@@ -94,13 +92,6 @@ __global__ __launch_bounds__(64 * kRowWaves) void k_edt_rows(const void* __restr
     if (j < W) out[j] = pick;
     if (m) carry = c * 64 + 63 - __builtin_clzll(m);
   }
-}
-
-// floor(n / d) for d > 0
-__device__ __forceinline__ int edt_floor_div(int n, int d) {
-  int q = n / d;
-  if (n - q * d < 0) --q;
-  return q;
 }
 
 // `image` holds the row pass's seed columns on entry and dist2 on exit: a column is read whole (down) before any of it is
@@ -190,11 +181,11 @@ __global__ __launch_bounds__(kColThreads) void k_edt_cols(int32_t* image, uint2*
   }
 }
 
-// The two passes over n_frames frames of H x W (n_frames H W <= kEdtGroupPixels), on `stream`: no allocation, no
-// synchronisation, no atomics.  seed: u8 (kind 0, seed iff != 0) or int32 (kind 1, seed iff >= 0), seed_stride elements between
-// frames; workspace: kEdtWorkspaceInts ints per pixel, 8-byte aligned; dist2, nearest (may be NULL): dense [n_frames][H][W].
-void edt_launch(const void* seed, int kind, long long seed_stride, int n_frames, int invert, int W, int H, int32_t* workspace,
-                int32_t* dist2, int32_t* nearest, hipStream_t stream) {
+}  // namespace
+
+// The two passes over n_frames frames of H x W (edt.h: the volume distance transform runs them over its slices too).
+void bodyfit::edt_launch(const void* seed, int kind, long long seed_stride, int n_frames, int invert, int W, int H,
+                         int32_t* workspace, int32_t* dist2, int32_t* nearest, hipStream_t stream) {
   const long long n_rows = (long long)n_frames * H, n_cols = (long long)n_frames * W;
   uint2* stack = reinterpret_cast<uint2*>(workspace);              // [n_frames][H][W] entries
   int32_t* col = dist2;                                            // the seed columns pass through the output image
@@ -205,8 +196,6 @@ void edt_launch(const void* seed, int kind, long long seed_stride, int n_frames,
     BODYFIT_LAUNCH(k_edt_rows<1>, rgrid, dim3(64 * kRowWaves), 0, stream, seed, seed_stride, W, H, n_rows, invert, col);
   BODYFIT_LAUNCH(k_edt_cols, cgrid, dim3(kColThreads), 0, stream, dist2, stack, W, H, n_cols, nearest);
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,5 +1,6 @@
-// volume.h — what api_volume.hip (the host side of bodyfit_volume_sample_device, bodyfit_volume_integrate_device and
-// bodyfit_volume_surface_*) launches from k_volume.hip, k_tsdf.hip and k_surface_extract.hip.
+// volume.h — what api_volume.hip (the host side of bodyfit_volume_sample_device, bodyfit_volume_integrate_device,
+// bodyfit_volume_surface_* and bodyfit_volume_distance_*) launches from k_volume.hip, k_tsdf.hip, k_surface_extract.hip and
+// k_edt3.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -84,5 +85,42 @@ inline SurfaceWorkspace surface_workspace(long long n_voxels, long long F) {
 void launch_surface_count(const SurfaceArgs& a, hipStream_t st);
 // bodyfit_volume_surface_emit_device: k_mc_emit
 void launch_surface_emit(const SurfaceArgs& a, hipStream_t st);
+
+
+struct DistanceArgs {
+  int nx, ny, nz;                 // each <= kDistanceMaxDim
+  int F;                          // volumes
+  const void* seed;               // u8 (kind 0, seed iff != 0) or int32 (kind 1, seed iff >= 0), seed_stride elements between volumes
+  int kind, invert;
+  long long seed_stride;
+  void* workspace;                // distance_workspace(nx ny nz, F).bytes, 8-byte aligned
+  int* dist2;                     // [F][nz][ny][nx]
+  int* nearest;                   // the same shape, or null
+};
+
+constexpr int kDistanceMaxDim = 16384;
+// voxels of the largest group of volumes transformed by one round of launches: 16 bytes each, 4 GiB of workspace (a single
+// larger volume is a group of its own)
+constexpr long long kDistanceGroupVoxels = 1ll << 28;
+
+// the byte offsets of the workspace's arrays for F volumes of n_voxels voxels, its size, and the volumes per group: the envelope
+// stack that the xy and the z stage share (8 bytes per voxel), then the slices' 2-D results d2 and n2 (4 each)
+struct DistanceWorkspace { long long stack, d2, n2, bytes; int group; };
+inline DistanceWorkspace distance_workspace(long long n_voxels, long long F) {
+  DistanceWorkspace w;
+  long long group = kDistanceGroupVoxels / n_voxels;
+  group = group < 1 ? 1 : group;
+  group = group > F ? F : group;
+  w.group = (int)group;
+  w.stack = 0;
+  w.d2 = 8 * group * n_voxels;
+  w.n2 = w.d2 + 4 * group * n_voxels;
+  w.bytes = w.n2 + 4 * group * n_voxels;
+  return w;
+}
+
+// bodyfit_volume_distance_device: k_edt_rows, k_edt_cols over the slices and k_edt_depth over the columns of the a.F > 0 volumes,
+// group after group on `st`
+void launch_volume_distance(const DistanceArgs& a, hipStream_t st);
 
 }  // namespace bodyfit

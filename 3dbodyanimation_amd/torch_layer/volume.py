@@ -9,12 +9,18 @@ or a per-frame distance volume of a scan, an object to touch).  The names are re
     floor = volume.VolumeTerm(sdf, origin, spacing, mode="inside")                      # penetration: only inside costs
     soles = volume.VolumeTerm(sdf, origin, spacing, mode="zero", vertex_ids=sole_ids)   # contact: pulled to the zero level
     (obj.cost(obj(x, beta)) + w * floor(layer(x, beta)[0])).backward()
+    dist2, nearest = volume.distance_transform(mask)                                    # exact, int32, in index units
+    room = volume.esdf(sdf, spacing, trunc=0.05)                                        # a TSDF made a distance outside its band
+    hull = volume.occupancy_sdf(inside, spacing)                                        # a mask made a signed distance field
     cost, g, H = floor.normal_equations(layer, x, beta)                                 # needs faces=...
 
 sample_volume is bodyfit_volume_sample_device (k_volume.hip: one trilinear read per (frame, point), O(V) gathers per frame whatever
 the scene's size, and the exact derivative of the cell's patch in world units; include/bodyfit.h states the definition and its
 bounds).  A point outside the volume, a gated point and a point whose cell holds a voxel that is not finite (a TSDF's unobserved
 space) is dead: value 0, no gradient, no cost.
+
+distance_transform is bodyfit_volume_distance_device (k_edt3.hip: the 2-D feature transform of k_edt.hip over the slices, then one
+lane per (j, i) column along z; integers, exact, no atomics); esdf and occupancy_sdf are two transforms each and elementwise torch.
 
 integrate_tsdf is bodyfit_volume_integrate_device (k_tsdf.hip: one lane per voxel, the running average of the projective distance
 along the optical axis, the state in registers over the frames of a call and rounded to f32 after each, so that one call with F
@@ -24,10 +30,11 @@ extract_surface is bodyfit_volume_surface_count_device / _emit_device (k_surface
 per-voxel counts, a device-wide exclusive scan and an indexed emit with welded vertices; the table is derived by
 tools/gen_mc_table.py).  Its mesh is what render_depth, closest_surface, SurfaceTerm, winding_number and vertex_normals take.
 
-NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, a 3-D distance
-transform; for the fusion: the Euclidean ray length as the measure, a bilinear depth lookup, per-pixel weights, colour volumes;
-for the extraction: vertex normals or colours from the volume, the gradient of the vertices in the voxels, decimation, a
-capacity-only single call without the host synchronisation.
+NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume; for the
+distance transform: anisotropic metrics, sub-voxel seed positions, its gradients, a banded voxelize_sdf; for the fusion: the
+Euclidean ray length as the measure, a bilinear depth lookup, per-pixel weights, colour volumes; for the extraction: vertex
+normals or colours from the volume, the gradient of the vertices in the voxels, decimation, a capacity-only single call without
+the host synchronisation.
 """
 from __future__ import annotations
 
@@ -295,6 +302,142 @@ def extract_surface(volume: torch.Tensor, origin, spacing, iso: float = 0.0, wei
             raise ValueError(f"{n_verts} vertices and {n_faces} faces in one batch: int32 offsets cannot hold them, extract fewer volumes per call")
         return verts, faces, offsets[0].to(torch.int32), offsets[1].to(torch.int32)
     return verts, faces
+
+
+def distance_transform(seed: torch.Tensor, invert: bool = False, nearest: bool = True):
+    """The exact Euclidean distance transform WITH the nearest seed of volumes, in index units: (dist2, nearest), int32, of seed's
+    shape (nearest None when not asked).  seed: a GPU tensor [nz, ny, nx] or [F, nz, ny, nx]; torch.bool / torch.uint8: a voxel is
+    a seed iff it is != 0; torch.int32: a seed iff it is >= 0.  invert swaps seeds and non-seeds.  dist2[k, j, i] is the least
+    (k - k')^2 + (j - j')^2 + (i - i')^2 over the seeds of the same volume, in integers, with no tolerance; nearest = (k' ny + j')
+    nx + i' of a seed that attains it (among ties always the same one, not the lowest index); a volume without a seed holds
+    INT32_MAX and -1.  Every dimension is at most 16384.  A view whose volumes are farther apart than nz ny nx elements is used in
+    place.  No gradient; runs on torch.cuda.current_stream() without a host synchronisation, the workspace (16 bytes per voxel of
+    at most 2^28 voxels at a time) from torch's allocator (bodyfit_volume_distance_device, include/bodyfit.h; k_edt3.hip)."""
+    if not isinstance(seed, torch.Tensor) or seed.dtype not in (torch.bool, torch.uint8, torch.int32) or not seed.is_cuda:
+        raise TypeError("seed must be a bool, uint8 or int32 tensor on the GPU")
+    if seed.ndim not in (3, 4) or min(seed.shape[-3:]) < 1:
+        raise ValueError(f"seed must be [nz, ny, nx] or [F, nz, ny, nx] with nz, ny, nx >= 1, got {tuple(seed.shape)}")
+    m = seed.detach()
+    batched = m.ndim == 4
+    if not batched:
+        m = m.unsqueeze(0)
+    F, nz, ny, nx = m.shape
+    n = nz * ny * nx
+    if not (m.stride(3) == 1 and m.stride(2) == nx and m.stride(1) == ny * nx and (F <= 1 or m.stride(0) >= n)):
+        m = m.contiguous()
+    stride = m.stride(0) if F > 1 else n
+    dev = m.device
+    dist2 = torch.empty((F, nz, ny, nx), dtype=torch.int32, device=dev)
+    near = torch.empty((F, nz, ny, nx), dtype=torch.int32, device=dev) if nearest else None
+    if F > 0:
+        handle = _volume_handle(dev.index, (nx, ny, nz), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+        with torch.cuda.device(dev):
+            work = torch.empty(handle.distance_layout(F), dtype=torch.uint8, device=dev)
+            handle.distance_device(m.data_ptr(), 1 if m.dtype == torch.int32 else 0, stride, F, invert, work.data_ptr(),
+                                   dist2.data_ptr(), near.data_ptr() if near is not None else None, stream=_stream())
+    if not batched:
+        return dist2[0], (near[0] if near is not None else None)
+    return dist2, near
+
+
+def _isotropic(spacing) -> float:
+    s = np.asarray(spacing, np.float64).reshape(-1)
+    if s.shape[0] not in (1, 3) or not np.all(np.isfinite(s)) or not np.all(s > 0.0):
+        raise ValueError("spacing is a finite positive float, or three of them")
+    if not np.all(s == s[0]):
+        raise ValueError(f"the distance transform is in index units: spacing must be isotropic, got {tuple(s)}")
+    return float(s[0])
+
+
+def _gather(values, index):
+    """values [F, n] at index [F, n] int32 (a -1 reads element 0: the caller masks it)"""
+    return torch.gather(values, 1, index.clamp(min=0).long())
+
+
+def esdf(tsdf: torch.Tensor, spacing, trunc: float, iso: float = 0.0, weight: torch.Tensor | None = None,
+         min_weight: float = 0.0) -> torch.Tensor:
+    """The Euclidean signed distance field of a TSDF ([nz, ny, nx] or [F, nz, ny, nx] f32 on the GPU, integrate_tsdf's): the TSDF
+    inside its band and a real distance everywhere else, f32 of tsdf's shape, so that VolumeTerm pulls a body that starts farther
+    than trunc from the surface and sample_volume has no dead space.  spacing must be isotropic (a float, or three equal ones),
+    otherwise ValueError.  DEFINITION, with phi the tsdf:
+      usable    a voxel is usable iff phi is finite and, with weight (tsdf's shape), its weight is >= min_weight;
+      inside    a usable voxel is inside iff phi < iso, as in extract_surface;
+      crossing  a usable voxel is a crossing iff phi == iso, or one of its 6 neighbours is usable and lies on the other side of iso
+                (one of the two is inside, the other is not);
+      (D, n) = distance_transform(crossings), (., m) = distance_transform(usable);
+      a    = spacing sqrt(D) + |phi(n) - iso|                      (to the nearest crossing voxel, plus what that voxel lacks)
+      sign = -1 where phi(m) < iso, else +1                        (the voxel's own side where it is usable: m is itself)
+      out  = phi - iso   where the voxel is usable and |phi - iso| < trunc,
+             sign a      elsewhere;
+    a volume without a crossing is all NaN.  Two transforms and elementwise torch in f64, rounded once to f32.  trunc is rounded
+    to f32 before the comparison: the fusion's cap is the f32 nearest to its trunc, and a voxel AT the cap is outside the band.
+    With iso != 0 the band is still measured from iso: pass at most the fusion's trunc less |iso|.
+
+    What it is not: it is the distance to the nearest OBSERVED crossing voxel, so outside the band it is an UPPER estimate of the
+    distance to the surface (the surface may be nearer where no frame has seen it, and the path to a voxel centre plus that
+    voxel's own distance is never shorter than the straight line).  Space that no frame has seen takes its sign from the nearest
+    observed voxel, which can be wrong deep inside an unobserved block next to both sides.  No gradient; runs on
+    torch.cuda.current_stream() without a host synchronisation."""
+    s = _isotropic(spacing)
+    if not isinstance(tsdf, torch.Tensor) or tsdf.dtype != torch.float32 or not tsdf.is_cuda:
+        raise TypeError("tsdf must be a float32 tensor on the GPU")
+    if tsdf.ndim not in (3, 4) or min(tsdf.shape[-3:]) < 1:
+        raise ValueError(f"tsdf must be [nz, ny, nx] or [F, nz, ny, nx], got {tuple(tsdf.shape)}")
+    trunc, iso, min_weight = float(trunc), float(iso), float(min_weight)
+    if not trunc > 0.0 or not np.isfinite(iso) or np.isnan(min_weight):
+        raise ValueError("trunc must be positive, iso finite and min_weight a number")
+    phi = tsdf.detach()
+    batched = phi.ndim == 4
+    if not batched:
+        phi = phi.unsqueeze(0)
+    usable = torch.isfinite(phi)
+    if weight is not None:
+        if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.device != tsdf.device:
+            raise TypeError("weight must be a float32 tensor on the GPU of tsdf, or None")
+        if weight.shape != tsdf.shape:
+            raise ValueError(f"weight must have the tsdf's shape {tuple(tsdf.shape)}, got {tuple(weight.shape)}")
+        usable = usable & (weight.detach().reshape(phi.shape) >= min_weight)
+    inside = usable & (phi < iso)
+    crossing = usable & (phi == iso)
+    for axis in (1, 2, 3):
+        n = phi.shape[axis]
+        if n < 2:
+            continue
+        flip = (usable.narrow(axis, 0, n - 1) & usable.narrow(axis, 1, n - 1)
+                & (inside.narrow(axis, 0, n - 1) != inside.narrow(axis, 1, n - 1)))
+        crossing.narrow(axis, 0, n - 1).logical_or_(flip)
+        crossing.narrow(axis, 1, n - 1).logical_or_(flip)
+    D, near = distance_transform(crossing)
+    _, own = distance_transform(usable)
+    F = phi.shape[0]
+    rel = phi.reshape(F, -1).double() - iso
+    a = s * D.reshape(F, -1).double().sqrt() + _gather(rel, near.reshape(F, -1)).abs()
+    negative = _gather(rel, own.reshape(F, -1)) < 0.0
+    out = torch.where(negative, -a, a)
+    band = usable.reshape(F, -1) & (rel.abs() < float(np.float32(trunc)))
+    out = torch.where(band, rel, out)
+    out = torch.where((near.reshape(F, -1) < 0), torch.full_like(out, float("nan")), out)
+    out = out.to(torch.float32).reshape(phi.shape)
+    return out if batched else out[0]
+
+
+def occupancy_sdf(inside: torch.Tensor, spacing) -> torch.Tensor:
+    """The signed distance field of an occupancy mask (inside: torch.bool [nz, ny, nx] or [F, nz, ny, nx] on the GPU; a visual hull,
+    a segmented scan), f32 of its shape, NEGATIVE inside, the surface taken half a voxel off the voxel centres on either side:
+      an outside voxel:  spacing (sqrt(dist2 to the nearest inside voxel)  - 1/2),
+      an inside voxel:  -spacing (sqrt(dist2 to the nearest outside voxel) - 1/2),
+    from two distance_transform calls, in f64, rounded once to f32.  A volume that is all inside or all outside is all NaN.
+    spacing must be isotropic (a float, or three equal ones), otherwise ValueError.  No gradient."""
+    s = _isotropic(spacing)
+    if not isinstance(inside, torch.Tensor) or inside.dtype != torch.bool or not inside.is_cuda:
+        raise TypeError("inside must be a bool tensor on the GPU")
+    to_in, _ = distance_transform(inside, nearest=False)
+    to_out, _ = distance_transform(inside, invert=True, nearest=False)
+    m = inside.detach()
+    d = torch.where(m, to_out, to_in).double().sqrt()
+    out = torch.where(m, -s * (d - 0.5), s * (d - 0.5))
+    none = (torch.maximum(to_in, to_out) == torch.iinfo(torch.int32).max).flatten(-3).any(dim=-1)[..., None, None, None]
+    return torch.where(none, torch.full_like(out, float("nan")), out).to(torch.float32)
 
 
 class VolumeTerm(_TermHandles, torch.nn.Module):

@@ -1750,8 +1750,8 @@ void bodyfit_volume_destroy(bodyfit_volume* h);
  * n_points == 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle, negative n_frames or n_points, and
  * with points to write: NULL d_points / d_volume / d_value / d_valid, a point stride below 3 n_points, a volume stride that is
  * neither 0 nor >= nx ny nz, 2^39 points or more.
- * NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, a 3-D distance
- * transform, and the entries of the C++ mirror header.                                                                          */
+ * NOT BUILT: the gradient in the voxels, multi-channel volumes, i16 / f16 storage, extrapolation outside the volume, and the
+ * entries of the C++ mirror header.                                                                                             */
 int bodyfit_volume_sample_device(bodyfit_volume* h, const float* d_points, long long points_frame_stride, long long n_points,
                                  int n_frames, const float* d_volume, long long volume_frame_stride,
                                  const uint8_t* d_gate /* may be NULL */, float* d_value, uint8_t* d_valid,
@@ -1875,6 +1875,46 @@ int bodyfit_volume_surface_emit_device(bodyfit_volume* h, const float* d_volume,
                                        long long volume_frame_stride, int n_volumes, float iso, float min_weight,
                                        void* d_workspace, const long long* d_offsets, long long vert_capacity,
                                        long long face_capacity, float* d_verts, int32_t* d_faces, void* stream);
+/* VOLUME DISTANCE TRANSFORM with the nearest seed (a 3-D feature transform) of n_volumes masks of the handle's dims (k_edt3.hip over
+ * k_edt.hip): a full distance field from a mask (a visual hull, a segmented scan) or from the crossings of a TSDF, where the TSDF
+ * itself is a distance only inside its band.  The seed kinds are those of bodyfit_raster_distance_device: seed_kind 0, d_seed is
+ * u8 [n_volumes][nz][ny][nx] and a voxel is a SEED iff its byte is != 0; seed_kind 1, int32 and a seed iff its value is >= 0.
+ * seed_volume_stride elements (bytes or int32) between volumes, >= nx ny nz.  invert != 0 swaps seeds and non-seeds.  Outputs
+ * d_dist2 and, unless NULL, d_nearest: int32 [n_volumes][nz][ny][nx], dense, volume after volume.
+ * DEFINITION, exact, in integers and in INDEX units (the handle's spacing and origin are not used), for voxel (k, j, i) of volume v:
+ *   dist2[v][k][j][i]   = min over the seeds (k', j', i') of volume v of (k - k')^2 + (j - j')^2 + (i - i')^2,
+ *   nearest[v][k][j][i] = (k' ny + j') nx + i' of a seed that ATTAINS that minimum.
+ * A seed voxel has dist2 0 and nearest itself.  A volume without a seed gets dist2 = INT32_MAX and nearest = -1 at every voxel.
+ * Range: EVERY DIMENSION IS AT MOST 16384 (a larger one: BODYFIT_ERR_INVALID), so dist2 <= 3 x 16383^2 < 2^30; g below is a 2-D
+ * dist2 <= 2 x 16383^2 < 2^29, a squared slice difference is < 2^28, so each side of the comparison below is < 2^28 + 2^29 < 2^30
+ * and the numerator of the division is |u^2 - s^2| + |g_u - g_s| < 2^28 + 2^29 < 2^30 in magnitude: int32 throughout.
+ * TIE RULE.  Among the seeds at the minimum the choice is a fixed function of the volume's mask: inside a slice the rule of
+ * bodyfit_raster_distance_device; along z the slice that entered the lower envelope first keeps every voxel at which a later
+ * slice only equals it.  So nearest is always the same one, but it is not "the lowest index": use it as A nearest seed.
+ * CONTRACT.  No tolerance: dist2 equals the definition at every voxel, and nearest is a seed of the same volume at exactly that
+ * squared distance.  Every output element is written, whatever the outputs held.  No atomics, plain stores: bit-identical from run
+ * to run, and a volume's outputs depend on that volume only (identical whatever n_volumes and the stride).
+ * Derivation.  Stage xy is the 2-D transform of each slice k (a frame of W = nx, H = ny): d2(k, j, i), the minimum over the seeds
+ * of slice k alone, INT32_MAX in a slice without a seed, and n2 = j' nx + i'.  Then dist2(x, j, i) = min_k F_k(x), F_k(x) =
+ * (x - k)^2 + d2(k, j, i) over the slices that have a seed: the column pass of the 2-D transform with an ARBITRARY g_k = d2(k),
+ * the same exact comparison F_s(t_s) <= F_u(t_s), the same true floor division for the first slice t_u at which u is strictly
+ * better, exact for the reason given there (an integer is <= a rational iff it is <= its floor).  Because g_s cannot be
+ * recomputed from the payload and is needed after slice s itself has been written on the way back (the reigning slice may lie
+ * above the voxel), the z pass does NOT run in place: g_s travels in the stack entry, d2 and n2 are read-only and the outputs are
+ * separate arrays.
+ * Shape: k_edt_rows and k_edt_cols unchanged over the n_volumes nz slices; k_edt_depth one lane per (volume, j, i) column,
+ * neighbouring lanes on neighbouring i.  bodyfit_volume_distance_layout: the bytes of the workspace for n_volumes volumes, 16 per
+ * voxel of a group (the stack that both stages share, d2, n2); a batch of more than 2^28 voxels is worked group after group
+ * of whole volumes on the stream, so the workspace stays at 4 GiB unless one volume alone is larger.  d_workspace is 8-byte
+ * aligned.  Asynchronous on `stream`, no host synchronisation, no allocation: the handle still owns no device memory.  n_volumes
+ * == 0: a successful no-op.  BODYFIT_ERR_INVALID (nothing is launched): NULL handle; negative n_volumes; a dimension above 16384;
+ * seed_kind not 0 or 1; layout: NULL workspace_bytes; with volumes to write: NULL d_seed / d_dist2 / d_workspace, a workspace that
+ * is not 8-byte aligned, a stride below nx ny nz.
+ * NOT BUILT: anisotropic metrics, sub-voxel seed positions, gradients of the transform, the entries of the C++ mirror header.   */
+int bodyfit_volume_distance_layout(bodyfit_volume* h, int n_volumes, long long* workspace_bytes);
+int bodyfit_volume_distance_device(bodyfit_volume* h, const void* d_seed, int seed_kind, long long seed_volume_stride,
+                                   int n_volumes, int invert, void* d_workspace, int32_t* d_dist2,
+                                   int32_t* d_nearest /* may be NULL */, void* stream);
 
 /* kernels launched by this process through the library so far (benchmarks: launches per LM iteration) */
 long bodyfit_launch_count(void);
