@@ -664,7 +664,7 @@ static int solve_impl(bodyfit_problem* p, double* frame_params, double* beta, co
   for (size_t gi = 0; gi < groups.size(); ++gi) {
     Group& g = groups[gi];
     g.cost = g.initial_cost = group_cost(c, g, r.data());
-    if (!std::isfinite(g.cost)) { g.active = false; g.termination = 2; g.why = "initial cost is not finite"; }
+    if (!lm_cost_finite(g.cost)) { g.active = false; g.termination = 2; g.why = "initial cost is not finite"; }
   }
   // BODYFIT_TIMING=1: where the host loop's wall time goes (diagnostic print at the end of the solve)
   const bool timing = std::getenv("BODYFIT_TIMING") != nullptr;

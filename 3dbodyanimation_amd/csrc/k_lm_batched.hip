@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_lm_init(LmProblem P, LmState S, const d
     S.radius[f] = kLmInitialRadius;
     S.dec[f] = kLmInitialDecrease;
     int fl = kLmActive;
-    if (!(c == c) || c > 1e300) fl = (2 << kLmTermShift);   // non-finite initial cost: failure
+    if (!lm_cost_finite(c)) fl = (2 << kLmTermShift);   // non-finite initial cost: failure
     S.flags[f] = fl;
     S.iters[f] = 0; S.n_ok[f] = 0; S.n_bad[f] = 0;
     if (fl & kLmActive) atomicAdd(S.active_count, 1);

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(1024) void k_win_init(WinProblem P, WinBuf W, const
     double* st = W.status;
     st[kWsCost] = c; st[kWsInitialCost] = c; st[kWsRadius] = kLmInitialRadius; st[kWsDec] = kLmInitialDecrease; st[kWsModel] = 0.0;
     st[kWsHasCand] = 0.0; st[kWsIters] = 0.0; st[kWsOk] = 0.0; st[kWsBad] = 0.0;
-    const bool finite = (c == c) && c < 1e300;
+    const bool finite = lm_cost_finite(c);
     st[kWsActive] = finite ? 1.0 : 0.0;
     st[kWsTermination] = finite ? 1.0 : 2.0;
     st[kWsAccepted] = 1.0; st[kWsGmax] = 0.0; st[kWsNewCost] = c; st[kWsJsel] = 0.0;

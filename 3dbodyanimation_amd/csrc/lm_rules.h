@@ -24,10 +24,13 @@ constexpr double kLmGradientTolerance = 1e-10;
 constexpr double kLmParameterTolerance = 1e-8;
 constexpr double kLmCostLimit = 1e300;          // a cost at or above it counts as not finite
 
-// rho = (cost - new_cost) / model_change.  (A cost is a sum of squares and Huber terms, never negative, so `finite` is written
-// as "not NaN and below the limit" everywhere: -inf, the one input std::isfinite would treat differently, cannot occur.)
+// The one finite-cost predicate: the initial cost of a solve (not finite: failure before the first iteration) and the cost at
+// every candidate (not finite: rejected).  (A cost is a sum of squares and Huber terms, never negative, so `finite` is written
+// as "not NaN and below the limit": -inf, the one input std::isfinite would treat differently, cannot occur.)
+LM_RULE_FN bool lm_cost_finite(double cost) { return (cost == cost) && cost < kLmCostLimit; }
+// rho = (cost - new_cost) / model_change
 LM_RULE_FN bool lm_step_accepted(double new_cost, double model_change, double rho) {
-  return (new_cost == new_cost) && new_cost < kLmCostLimit && model_change > 0.0 && rho > kLmMinRelativeDecrease;
+  return lm_cost_finite(new_cost) && model_change > 0.0 && rho > kLmMinRelativeDecrease;
 }
 LM_RULE_FN double lm_radius_after_accept(double radius, double rho) {
   const double t = 2.0 * rho - 1.0;

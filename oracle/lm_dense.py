@@ -18,6 +18,12 @@ import numpy as np
 from . import oracle as O
 
 NP_ = 76
+COST_LIMIT = 1e300      # lm_rules.h kLmCostLimit: a cost at or above it counts as not finite
+
+
+def cost_finite(cost):
+    """lm_rules.h lm_cost_finite: not NaN and below the limit (a cost is never negative, so -inf cannot occur)"""
+    return bool(cost == cost and cost < COST_LIMIT)
 
 
 def _rows(om, seq, x, beta, n_cols, use_shape, pose_blend, beta_pose, ogmm, beta_shape, lam, huber, want_jac, jac_mode=0):
@@ -128,6 +134,11 @@ def _rows_sparse(om, seq, x, beta, n_cols, use_shape, pose_blend, beta_pose, ogm
 def solve(om, seq, x0, beta0, n_cols=86, use_shape=True, pose_blend=True, beta_pose=0.0, ogmm=None, beta_shape=0.0,
           lam=0.0, huber=3.0, max_iters=100, constant=None, scale_bounds=(0.3, 3.0), verbose=False, jac_mode=0, sparse=False):
     """One problem over all frames of `seq` with a shared beta.  Returns x, beta, info.
+    info: initial_cost, final_cost, iterations, n_ok, n_bad, termination (0 convergence, 1 iteration limit, 2 failure),
+    why (gradient | parameter | function | iterations | initial_cost | radius: the test that ended the solve) and trace, one
+    dict per iteration that reached a decision: radius (before the decision), accepted, projected (a scale was clipped to
+    its bound), and rho, model, cost (at the candidate) -- None for a failed factorisation, which counts as a rejection.
+    A non-finite initial cost ends the solve at once: termination 2, no iteration, the parameters untouched.
     jac_mode 0: analytic Jacobian; 1: the reference's stride-4 dual-number passes (DynamicAutoDiffCostFunction).
     sparse: scipy.sparse Jacobian / normal equations and a sparse LU (no pivoting: its diagonal is positive exactly when the
     dense Cholesky would succeed) instead of dense algebra — same rows, same LM."""
@@ -142,7 +153,11 @@ def solve(om, seq, x0, beta0, n_cols=86, use_shape=True, pose_blend=True, beta_p
             free[f * NP_:(f + 1) * NP_] = ~np.asarray(constant, bool)
     args = (n_cols, use_shape, pose_blend, beta_pose, ogmm, beta_shape, lam, huber)
     cost, r, J = rows_fn(om, seq, x, beta, *args, True, jac_mode)
-    info = dict(initial_cost=cost, iterations=0, n_ok=0, n_bad=0, termination=1)
+    info = dict(initial_cost=cost, iterations=0, n_ok=0, n_bad=0, termination=1, why="iterations", trace=[])
+    if not cost_finite(cost):
+        info.update(termination=2, why="initial_cost", final_cost=cost)
+        return x, beta, info
+    trace = info["trace"]
     radius, dec = 1e4, 2.0
     scale = None
     for it in range(max_iters):
@@ -156,7 +171,7 @@ def solve(om, seq, x0, beta0, n_cols=86, use_shape=True, pose_blend=True, beta_p
             s0 = x[f, 0]
             gp[f * NP_] = s0 - np.clip(s0 - g[f * NP_], *scale_bounds)
         if np.abs(gp[free]).max() <= 1e-10:
-            info["termination"] = 0; break
+            info["termination"] = 0; info["why"] = "gradient"; break
         gs = g * scale
         idx = np.where(free)[0]
         try:
@@ -178,23 +193,30 @@ def solve(om, seq, x0, beta0, n_cols=86, use_shape=True, pose_blend=True, beta_p
                 L = np.linalg.cholesky(Hd[np.ix_(idx, idx)])
                 ds[idx] = -np.linalg.solve(L.T, np.linalg.solve(L, gs[idx]))
         except (np.linalg.LinAlgError, RuntimeError):
+            trace.append(dict(radius=radius, accepted=False, projected=False, rho=None, model=None, cost=None))
             radius /= dec; dec *= 2; info["n_bad"] += 1; info["iterations"] += 1
+            if radius < 1e-32:
+                info["termination"] = 2; info["why"] = "radius"; break
             continue
         d = ds * scale
         xn = x + d[:F * NP_].reshape(F, NP_)
         clipped = np.clip(xn[:, 0], *scale_bounds)
-        if np.any(clipped != xn[:, 0]):
+        projected = bool(np.any(clipped != xn[:, 0]))
+        if projected:
             d[np.arange(F) * NP_] = clipped - x[:, 0]
             xn[:, 0] = clipped
         bn = beta + d[F * NP_:] if nb else beta
         model = -(d @ g) - 0.5 * d @ (H @ d)
         if np.linalg.norm(d) <= 1e-8 * (np.sqrt((x ** 2).sum() + (beta ** 2).sum()) + 1e-8):
-            info["termination"] = 0; break
+            info["termination"] = 0; info["why"] = "parameter"; break
         new_cost, rn, _ = rows_fn(om, seq, xn, bn, *args, False)
         info["iterations"] += 1
         change = cost - new_cost
         rho = change / model
-        if np.isfinite(new_cost) and model > 0 and rho > 1e-3:
+        accepted = bool(cost_finite(new_cost) and model > 0 and rho > 1e-3)
+        trace.append(dict(radius=radius, accepted=accepted, projected=projected, rho=float(rho), model=float(model),
+                          cost=float(new_cost)))
+        if accepted:
             x, beta = xn, bn
             old = cost
             cost, r, J = rows_fn(om, seq, x, beta, *args, True, jac_mode)
@@ -203,10 +225,10 @@ def solve(om, seq, x0, beta0, n_cols=86, use_shape=True, pose_blend=True, beta_p
             if verbose:
                 print(f"[dense-lm] it {info['iterations']} cost {cost:.6e} rho {rho:.3f} radius {radius:.2e}")
             if abs(change) < 1e-6 * old:
-                info["termination"] = 0; break
+                info["termination"] = 0; info["why"] = "function"; break
         else:
             radius /= dec; dec *= 2; info["n_bad"] += 1
             if radius < 1e-32:
-                info["termination"] = 2; break
+                info["termination"] = 2; info["why"] = "radius"; break
     info["final_cost"] = cost
     return x, beta, info

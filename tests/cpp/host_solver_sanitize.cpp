@@ -165,6 +165,51 @@ int main(int argc, char** argv) {
     std::printf("pose only: rc %d cost %.6e -> %.6e\n", rc, s[0].initial_cost, s[0].final_cost);
     if (rc != BODYFIT_OK || !(s[0].final_cost < s[0].initial_cost)) ++bad;
   }
+  {   // (d) off the happy path: every frame from a far start (joints and root of ~1 rad) -- rejected steps, runs of them, the
+      //     doubling of the shrink factor and its reset (tests/lm_cases.py holds the cases the GPU suite compares)
+    bodyfit_problem p = make(76, false, 20.0, 0.0, 0.0);
+    std::vector<double> x;
+    init(x);
+    for (int i = 0; i < F; ++i) {
+      for (int c = 1; c < 4; ++c) x[(size_t)i * 76 + c] = 1.2 * std::sin(2.1 * c + 0.9 * i + 0.4);
+      for (int c = 7; c < 76; ++c) x[(size_t)i * 76 + c] = 1.2 * std::sin(1.3 * c + 0.7 * i);
+    }
+    bodyfit_fit_options opt{25, 0.3, 3.0, 0, 1};
+    std::vector<bodyfit_fit_summary> s(F);
+    const int rc = bodyfit_solve(&p, x.data(), nullptr, nullptr, 1, &opt, s.data(), F);
+    if (rc != BODYFIT_OK) ++bad;
+    int rejected = 0;
+    for (int i = 0; i < F; ++i) {
+      std::printf("far start: frame %d iterations %d = %d accepted + %d rejected, termination %d, cost %.6e -> %.6e\n", i,
+                  s[i].iterations, s[i].n_successful, s[i].n_unsuccessful, s[i].termination, s[i].initial_cost, s[i].final_cost);
+      if (s[i].iterations != s[i].n_successful + s[i].n_unsuccessful || s[i].iterations > 25 || !s[i].usable ||
+          !(s[i].final_cost < s[i].initial_cost))
+        ++bad;
+      rejected += s[i].n_unsuccessful;
+    }
+    if (rejected < 3) ++bad;
+  }
+  if (F >= 4) {   // (e) the failure branch: one observed coordinate is NaN, another frame's infinite -- those frames fail before the first
+      //     iteration and come back untouched, the others are fitted
+    bodyfit_problem p = make(76, false, 20.0, 0.0, 0.0);
+    p.uv[2 * (size_t)koff[1] + 6] = std::nan("");
+    p.uv[2 * (size_t)koff[2] + 3] = INFINITY;
+    std::vector<double> x;
+    init(x);
+    const std::vector<double> x0 = x;
+    bodyfit_fit_options opt{10, 0.3, 3.0, 0, 1};
+    std::vector<bodyfit_fit_summary> s(F);
+    const int rc = bodyfit_solve(&p, x.data(), nullptr, nullptr, 1, &opt, s.data(), F);
+    std::printf("nan / inf frames: rc %d terminations %d %d %d %d\n", rc, s[0].termination, s[1].termination, s[2].termination,
+                s[3].termination);
+    if (rc != BODYFIT_OK) ++bad;
+    for (int i = 0; i < F; ++i) {
+      const bool failed = i == 1 || i == 2;
+      const bool same = std::memcmp(&x[(size_t)i * 76], &x0[(size_t)i * 76], 76 * sizeof(double)) == 0;
+      if (failed && (s[i].termination != 2 || s[i].usable || s[i].iterations != 0 || !same)) ++bad;
+      if (!failed && (s[i].termination == 2 || !s[i].usable || !(s[i].final_cost < s[i].initial_cost) || same)) ++bad;
+    }
+  }
   oracle_model_destroy(om);
   std::printf(bad ? "host_solver_sanitize FAILED (%d)\n" : "host_solver_sanitize ok\n", bad);
   return bad ? 1 : 0;

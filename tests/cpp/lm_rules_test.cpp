@@ -29,6 +29,11 @@ int main() {
   CHECK(!lm_step_accepted(1.0, 0.0, 0.5));
   CHECK(!lm_step_accepted(1.0, -1.0, 0.5));
   CHECK(!lm_step_accepted(1.0, 1.0, nan));
+  // the finite-cost predicate (initial cost and candidates alike): not NaN and strictly below 1e300
+  CHECK(!lm_cost_finite(nan) && !lm_cost_finite(inf) && !lm_cost_finite(1e300));
+  CHECK(lm_cost_finite(9.999999999999999e+299) && !lm_cost_finite(1.0000000000000002e+300));   // the neighbours of 1e300
+  CHECK(std::nextafter(1e300, 0.0) == 9.999999999999999e+299 && std::nextafter(1e300, inf) == 1.0000000000000002e+300);
+  CHECK(lm_cost_finite(0.0) && lm_cost_finite(1.0) && !lm_cost_finite(std::numeric_limits<double>::max()));
   // radius after an accepted step: rho = 0.5 leaves it, rho = 1 triples it, the cap at 1e16 holds
   struct { double radius, rho; uint64_t want; } const acc[] = {
     {10000.0, 0.5, 0x40c3880000000000ull},
