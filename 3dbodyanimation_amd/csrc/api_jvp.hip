@@ -12,25 +12,27 @@ extern "C" {
 namespace {
 
 // the problem's JVP buffers, once (first JVP with a cloud tangent): its own mesh operands (so an evaluation's and the VJP's are
-// left alone), the primal blended vertices, and ONE 32-tangent tile per frame of transform tangents and coefficient fragments
-int jvp_problem_ready(bodyfit_problem* p) {
+// left alone), the primal blended vertices, and ONE 32-tangent tile per frame of transform tangents and coefficient fragments.
+// The clears are enqueued on the caller's stream `st`, in front of the launches that follow them there: a clear on the NULL
+// stream is not ordered against a non-blocking stream, and need not have completed when hipMemset returns.
+int jvp_problem_ready(bodyfit_problem* p, hipStream_t st) {
   if (p->jvp_alloc) return BODYFIT_OK;
   const bodyfit_model* m = p->m;
   const int F = p->d.F, nFT = p->d.nFTiles, nVT = m->d.nVTiles;
   const size_t nfa = (size_t)nFT * kBlendKSteps * 2 * 64 * 8, nsk = (size_t)nFT * kFTile * m->nJ * 12;
   HIP_TRY(p->mem.alloc(&p->jvp_mc.featA, nfa));
   HIP_TRY(p->mem.alloc(&p->jvp_mc.skinT, nsk));
-  HIP_TRY(hipMemset(p->jvp_mc.featA, 0, nfa * sizeof(uint16_t)));
-  HIP_TRY(hipMemset(p->jvp_mc.skinT, 0, nsk * sizeof(float)));
+  HIP_TRY(hipMemsetAsync(p->jvp_mc.featA, 0, nfa * sizeof(uint16_t), st));
+  HIP_TRY(hipMemsetAsync(p->jvp_mc.skinT, 0, nsk * sizeof(float), st));
   HIP_TRY(p->mem.alloc(&p->jvp_r, (size_t)std::max(1, p->lay.reproj_rows)));
   HIP_TRY(p->mem.alloc(&p->jvp_joints, (size_t)F * m->nJ * 3));
   HIP_TRY(p->mem.alloc(&p->jvp_bbuf, jvp_bbuf_elems(F, nVT)));
   HIP_TRY(p->mem.alloc(&p->jvp_tdot, jvp_tdot_elems(F)));
   HIP_TRY(p->mem.alloc(&p->jvp_featD, jvp_feat_elems(F)));
   HIP_TRY(p->mem.alloc(&p->jvp_dbuf, jvp_dbuf_elems(F, nVT)));
-  HIP_TRY(hipMemset(p->jvp_bbuf, 0, jvp_bbuf_elems(F, nVT) * sizeof(float)));
-  HIP_TRY(hipMemset(p->jvp_tdot, 0, jvp_tdot_elems(F) * sizeof(float)));
-  HIP_TRY(hipMemset(p->jvp_featD, 0, jvp_feat_elems(F) * sizeof(uint16_t)));
+  HIP_TRY(hipMemsetAsync(p->jvp_bbuf, 0, jvp_bbuf_elems(F, nVT) * sizeof(float), st));
+  HIP_TRY(hipMemsetAsync(p->jvp_tdot, 0, jvp_tdot_elems(F) * sizeof(float), st));
+  HIP_TRY(hipMemsetAsync(p->jvp_featD, 0, jvp_feat_elems(F) * sizeof(uint16_t), st));
   p->jvp_alloc = true;
   return BODYFIT_OK;
 }
@@ -64,7 +66,7 @@ int bodyfit_forward_offsets_jvp_device(bodyfit_problem* p, const double* d_frame
   const int per_frame = p->desc.beta_per_frame != 0, K = n_tangents;
   const bool mesh = d_tan_cloud != nullptr;
   if (mesh)
-    if (int rc = jvp_problem_ready(p)) return rc;
+    if (int rc = jvp_problem_ready(p, st)) return rc;
   p->async_stream = st;
   p->async_pending = true;
   const int n_tiles = (K + 31) / 32;

@@ -154,6 +154,9 @@ int bodyfit_problem_create(const bodyfit_model* m, const bodyfit_problem_desc* d
     const char* fe = std::getenv("BODYFIT_ONE_LAUNCH");
     p->fused_enabled = !(fe && fe[0] == '0');
   }
+  // the clears above run on the NULL stream and need not have completed when hipMemset returns; the problem's first caller may
+  // be a non-blocking stream, which is not ordered against the NULL stream: wait for them here, once per problem
+  HIP_TRY(hipStreamSynchronize(nullptr));
   *out = p.release();
   return BODYFIT_OK;
 }

@@ -286,6 +286,7 @@ static int solve_window_device(bodyfit_problem* p, double* frame_params, double*
     if (!p->win_pool || p->win_pool_bytes < off) {
       HIP_TRY(p->mem.alloc(&p->win_pool, off));
       HIP_TRY(hipMemset(p->win_pool, 0, off));
+      HIP_TRY(hipStreamSynchronize(nullptr));   // (the clear is on the NULL stream, the solve on a non-blocking one: as in bodyfit_problem_create)
       p->win_pool_bytes = off;
     }
     unsigned char* Bp = p->win_pool;

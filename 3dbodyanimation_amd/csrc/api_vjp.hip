@@ -57,7 +57,9 @@ int vjp_model_ready(const bodyfit_model* m, hipStream_t st) {
   return BODYFIT_OK;
 }
 
-int vjp_problem_ready(bodyfit_problem* p, bool mesh) {
+// the problem's VJP buffers, once; the clears of its mesh operands are enqueued on the caller's stream `st`, in front of the
+// launches that follow them there (a clear on the NULL stream is not ordered against a non-blocking stream)
+int vjp_problem_ready(bodyfit_problem* p, bool mesh, hipStream_t st) {
   const bodyfit_model* m = p->m;
   const int F = p->d.F, nFT = p->d.nFTiles, nVT = m->d.nVTiles;
   if (!p->vjp_alloc) {
@@ -68,8 +70,8 @@ int vjp_problem_ready(bodyfit_problem* p, bool mesh) {
     const size_t nfa = (size_t)nFT * kBlendKSteps * 2 * 64 * 8, nsk = (size_t)nFT * kFTile * m->nJ * 12;
     HIP_TRY(p->mem.alloc(&p->vjp_mc.featA, nfa));
     HIP_TRY(p->mem.alloc(&p->vjp_mc.skinT, nsk));
-    HIP_TRY(hipMemset(p->vjp_mc.featA, 0, nfa * sizeof(uint16_t)));
-    HIP_TRY(hipMemset(p->vjp_mc.skinT, 0, nsk * sizeof(float)));
+    HIP_TRY(hipMemsetAsync(p->vjp_mc.featA, 0, nfa * sizeof(uint16_t), st));
+    HIP_TRY(hipMemsetAsync(p->vjp_mc.skinT, 0, nsk * sizeof(float), st));
     HIP_TRY(p->mem.alloc(&p->vjp_r, (size_t)std::max(1, p->lay.reproj_rows)));
     HIP_TRY(p->mem.alloc(&p->vjp_joints, (size_t)F * m->nJ * 3));
     HIP_TRY(p->mem.alloc(&p->vjp_gb, vjp_gb_elems(nFT, nVT)));
@@ -111,7 +113,7 @@ int bodyfit_forward_offsets_vjp_device(bodyfit_problem* p, const double* d_frame
   const bool mesh = d_grad_cloud != nullptr;
   if (mesh)
     if (int rc = vjp_model_ready(m, st)) return rc;
-  if (int rc = vjp_problem_ready(p, mesh)) return rc;
+  if (int rc = vjp_problem_ready(p, mesh, st)) return rc;
   p->async_stream = st;
   p->async_pending = true;
   if (mesh) {

@@ -142,6 +142,9 @@ typedef struct bodyfit_problem_desc {
   int want_mesh;          /* also produce the 6890-vertex cloud per frame on each evaluation  */
 } bodyfit_problem_desc;
 
+/* Synchronous: allocates and uploads the problem's device state and clears what needs clearing on the NULL stream, and waits
+ * for those clears before it returns, so that the problem's first caller may be on any stream (a non-blocking stream is not
+ * ordered against the NULL stream).  A window solve that has to grow its pool clears it and waits in the same way, once. */
 int bodyfit_problem_create(const bodyfit_model* m, const bodyfit_problem_desc* desc, bodyfit_problem** out);
 void bodyfit_problem_destroy(bodyfit_problem* p);
 
